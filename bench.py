@@ -1,8 +1,18 @@
 """bench.py -- MonoDETR training throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision bf16|fp32] [--batch 8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--precision bf16|fp32] [--batch 8] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and nothing more: it builds the step, captures its graphs, runs the start-up
+(--prime) and W warm-up steps, times K steps and prints the line (metric, value, unit, ms_per_step = milliseconds of one timed
+step, dtype, config, final_loss).  --full adds everything else described below, as before: the per-kernel and roofline
+objects, the side measurements and the CPU baseline, run after the timed steps (with --graph off the per-kernel HIP events are
+recorded during the timed steps themselves, in --full runs only).  --dump-outputs DIR (one process) returns the timed step,
+after the timed steps, to the weights and optimizer state it started with, runs it once more the way it was timed (graph
+replay by default) and writes what that iteration handed back (dump_outputs()).  With the same arguments its inputs --
+initial weights, batch, dropout seeds -- are the same in every run, so that two runs, or two builds, can be compared output
+for output.
 
 A "step" is one pass of the hot path over one batch of synthetic input: MonoDETR forward in train
 mode (550 queries) -> SetCriterion (Hungarian matching + 8 losses x 3 decoder layers) -> backward ->
@@ -22,7 +32,7 @@ the list for A/B experiments (`config.switches` says what ran, `config.switch_so
   --config 2   ResNet-50 + input projections + MSDeformAttn encoder only, fp32, forward + backward   = BASELINE configs[1]
   --config 5   full step at 512 x 1760 with 100 (x 11) queries, bf16                                  = BASELINE configs[4]
 
-Extra objects on that line:
+Extra objects on that line (--full only):
   roofline      the dominant hand-written kernel (MSDA backward at the encoder shape): ALGORITHMIC
                 bytes per launch / its average launch duration measured with HIP
                 events on the launch stream during the timed steps, against 8 TB/s HBM.
@@ -208,6 +218,32 @@ class TrainStep(TrainIteration):
     def eager_iteration(self, batch=None):
         return super().eager_iteration(self.inputs if batch is None else batch)
 
+    def remember_initial_state(self):
+        """Copies of the weights and buffers before the first iteration, for restore_initial_state() (--dump-outputs)."""
+        self._initial = [t.detach().clone() for t in list(self.raw_model.parameters()) + list(self.raw_model.buffers())]
+
+    @torch.no_grad()
+    def restore_initial_state(self):
+        """Weights, buffers and optimizer state as they were before the first iteration, written in place (captured graphs keep
+        reading the same addresses): the remembered weights, zero moments, fp32 master copies of the initial bf16 weights, and
+        the device step counters at 0, so that the next update applies the first step's bias correction.  The host step counts
+        (checkpoint bookkeeping) and the dropout-seed counter go on as they are."""
+        opt = self.optimizer
+        params = list(self.raw_model.parameters())
+        for t, t0 in zip(params + list(self.raw_model.buffers()), self._initial):
+            t.copy_(t0)
+        for p, p0 in zip(params, self._initial):
+            st = opt.state.get(p, {})
+            for k in ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"):
+                if k in st:
+                    st[k].zero_()
+            if "master" in st:
+                st["master"].copy_(p0)
+        counters = [t for g in opt.param_groups for t in g.get("step_dev", {}).values()]
+        counters += [b["step_dev"] for b in (getattr(opt, "_flat", None) or (None, ()))[1] if "step_dev" in b]
+        for t in counters:
+            t.zero_()
+
 
 def time_variant(device, args, precision, switches, prime=10, timed=20, pg_init=None, **kw):
     """images/sec of another variant of the same step (the default path without optional kernels; the all-fp32 path),
@@ -233,6 +269,46 @@ def time_variant(device, args, precision, switches, prime=10, timed=20, pg_init=
     torch.cuda.empty_cache()
     return {"value": round(args.batch / dt, 2), "unit": "images/sec", "ms_per_step": round(dt * 1e3, 3), "steps": timed,
             "warmup": prime, "precision": precision, "switches": sorted(switches), "launch": launch}
+
+
+DUMP_PER_TENSOR = 8192                                               # --dump-outputs: positions sampled from a larger tensor
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(step, loss, out_dir, per_tensor=None, seed=0):
+    """--dump-outputs DIR: what the training iteration `step` handed its caller in its last call, as float32 .npy files --
+    loss.npy (the total loss), one <key>.npy per entry of the criterion's dict (``step.losses``), and the state that step left
+    in the model: parameters.npy (the weights its AdamW step wrote) and gradients.npy (the gradients it read, 0 where a
+    parameter received none).  Those two hold, tensor after tensor in ``named_parameters()`` order and in the tensor's logical
+    element order, every element of a tensor of at most `per_tensor` elements and a fixed sample of `per_tensor` positions of
+    a larger one (drawn from a generator seeded with `seed`: the same positions in every run and every build; `per_tensor`
+    defaults to DUMP_PER_TENSOR).  main() first returns the timed step to its initial state (TrainStep.restore_initial_state)
+    and runs it once more: the state after start-up + W + K iterations is not the same in two runs -- AdamW turns the rounding
+    differences of the step's floating-point atomics (their order does not repeat) into whole learning-rate steps of single
+    weights, and two runs of one build drifted apart by up to 4 % in the loss terms over 37 iterations.
+    Returns the bytes written."""
+    import re
+    import numpy as np
+    per_tensor = per_tensor or DUMP_PER_TENSOR
+    gen = torch.Generator().manual_seed(seed)
+    params, grads = [], []
+    for _, p in step.raw_model.named_parameters():
+        n = p.numel()
+        idx = (torch.arange(n) if n <= per_tensor else torch.randint(0, n, (per_tensor,), generator=gen)).to(p.device)
+        params.append(p.detach().reshape(-1)[idx].float())
+        grads.append(p.grad.detach().reshape(-1)[idx].float() if p.grad is not None else torch.zeros(idx.numel(), device=p.device))
+    arrays = {"loss": loss.detach().float().reshape(()), "parameters": torch.cat(params), "gradients": torch.cat(grads)}
+    for key, v in sorted((step.losses or {}).items()):
+        name = re.sub(r"[^A-Za-z0-9_.-]", "_", key)
+        assert name not in arrays, "criterion entry %r collides with another output" % key
+        arrays[name] = torch.as_tensor(v).detach().float()
+    host = {name: t.cpu().numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes exceed the dump limit" % total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def bind_to_gpu_numa_node(local_rank):
@@ -580,8 +656,14 @@ def main():
                          "(forward + backward | optimizer) around the eager RCCL all-reduce with N > 1 -- and fall back to eager "
                          "launches if the capture fails on any rank; on = the same without the fall-back; off = eager launches "
                          "(~1 900 per iteration: the step time then depends on the host CPU, 224-261 img/s across boxes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the fp32_path / default_path / rccl_1rank side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel / roofline / MFMA / family figures, the side "
+                         "measurements (fp32_path, eager_path, default_path, config2, config5, rccl_1rank) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed step once more from its initial weights and optimizer state and "
+                         "write what it computed to DIR/<name>.npy (dump_outputs())")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the fp32_path / default_path / rccl_1rank side measurements")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--cpu-batch", type=int, default=2)
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
@@ -592,6 +674,10 @@ def main():
     args = ap.parse_args()
     if args.cpu_baseline_child:
         return cpu_baseline_child(args.cpu_steps, args.cpu_batch)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("MDETR_BENCH_FORCE_DDP", "0") == "1"):
+        ap.error("--dump-outputs runs with one process (--gpus 1)")
     size, queries, part = (384, 1280), 50, "full"
     if args.config == 2:
         part = "encoder"
@@ -645,8 +731,11 @@ def main():
     _capi.lib()                                                     # fail loudly if the HIP library is missing
     # optional kernel families: the committed list (or the environment's MDETR_*=1 for an A/B run) -- the same on every rank
     chosen, switch_source = committed_switches(args.precision)
+
     step = TrainStep(device, args.batch, args.precision, ddp=sync_mode, local_rank=local_rank, graph=want_graph,
                      switches=chosen, size=size, queries=queries, part=part)
+    if args.dump_outputs:
+        step.remember_initial_state()
     launch_mode = "eager"
     if want_graph:                                                  # untimed: part of start-up, like model build
         if args.graph == "on":
@@ -672,7 +761,7 @@ def main():
     if dist_on:
         torch.distributed.barrier()
     torch.cuda.synchronize()
-    _capi.profile_enable(not use_graph)
+    _capi.profile_enable(args.full and not use_graph)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = step()
@@ -680,12 +769,17 @@ def main():
     if dist_on:
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
-    clocks = gpu_clocks(local_rank) if rank == 0 else None          # right after the timed region (the GPU still warm)
+    clocks = gpu_clocks(local_rank) if rank == 0 and args.full else None     # right after the timed region (the GPU still warm)
     gc.enable()
     _capi.profile_enable(False)
     loss = loss.clone()
+    if args.dump_outputs:
+        # one more iteration of the timed step itself (graph replay by default), from the weights and optimizer state it started
+        # with: the state after start-up + W + K iterations differs from run to run (dump_outputs())
+        step.restore_initial_state()
+        dump_outputs(step, step(), args.dump_outputs)
     kernel_timing = "HIP events around every launch of the timed steps"
-    if use_graph:
+    if use_graph and args.full:
         # events cannot be recorded inside a replayed graph: time the same kernels, same inputs, in a few
         # eager iterations right after the timed region
         _capi.profile_enable(True)
@@ -695,10 +789,10 @@ def main():
         torch.cuda.synchronize()
         _capi.profile_enable(False)
         kernel_timing = "HIP events around every launch of 3 eager iterations run right after the timed graph replays"
-    work_rows = _capi.profile_read_work()                       # (kind, key, launches, ms, MFLOP, KB) of those iterations
+    work_rows = _capi.profile_read_work() if args.full else []  # (kind, key, launches, ms, MFLOP, KB) of those iterations
     work_iters = 3 if use_graph else args.steps
     family_kernels, family_error = None, None
-    if hasattr(step, "eager_iteration") and os.environ.get("MDETR_BENCH_FAMILIES", "1") != "0":
+    if args.full and hasattr(step, "eager_iteration") and os.environ.get("MDETR_BENCH_FAMILIES", "1") != "0":
         # one more eager iteration under torch.profiler: every kernel's time.  EVERY rank runs it -- the iteration holds the
         # gradient exchange's collectives, which one rank alone would enter unmatched (a hang no try/except catches); rank 0's
         # table is the one reported
@@ -721,7 +815,7 @@ def main():
     msda_mixed = "MDETR_MSDA_BF16" in step.switches               # bf16-native operator: 2-byte value / out / grad_out
     MFMA_PEAK_TF = 2500.0                                            # dense bf16 (MI355X_MICROARCH.md; the headline 5 PF includes 2:1 sparsity)
     mfma_groups = {"attention_forward": [0.0, 0.0, 0], "attention_backward": [0.0, 0.0, 0], "convolutions": [0.0, 0.0, 0]}   # flop, ms, launches
-    for kind, key, launches, total_ms in _capi.profile_read():
+    for kind, key, launches, total_ms in (_capi.profile_read() if args.full else ()):
         avg = total_ms / max(launches, 1)
         if kind == 9:                                                # hand-written convolutions: key = MFLOP of the launch
             g = mfma_groups["convolutions"]
@@ -757,7 +851,7 @@ def main():
                         "frac": round(byts / total / 1e6 / 8000.0, 4)})
     # HBM traffic of the dominant operator: PMC counters cannot be read by the benchmarked process itself (rocprofv3 wraps a
     # command), so the figure comes from the committed PMC passes -- and only if they were taken on THIS kernel source
-    traffic, traffic_note = pmc_traffic()
+    traffic, traffic_note = pmc_traffic() if args.full else ({}, None)
     dom = max(ops, key=lambda o: o["ms"]) if ops else None
 
     if rank == 0:
@@ -798,11 +892,12 @@ def main():
         # the MFMA kernels of the step (north_star: "MFMA-utilisation ... against gfx950 peak"): useful FLOP of every launch of a
         # family / the HIP-event time of those launches, against the dense bf16 peak.  utilisation = achieved / peak (what the
         # MFMA-busy counter of profiles/*pmc_attn.json gives when divided by 1 024 SIMDs x kernel cycles)
-        line["mfma"] = {"peak_TFLOPs": MFMA_PEAK_TF, "dtype": "bf16", "timing": kernel_timing,
-                        **{k: {"TFLOPs": round(g[0] / g[1] / 1e9, 1), "utilisation": round(g[0] / g[1] / 1e9 / MFMA_PEAK_TF, 4),
-                               "launches_per_step": round(g[2] / (3 if use_graph else args.steps), 1),
-                               "ms_per_step": round(g[1] / (3 if use_graph else args.steps), 3)}
-                           for k, g in mfma_groups.items() if g[1] > 0}}
+        if args.full:
+            line["mfma"] = {"peak_TFLOPs": MFMA_PEAK_TF, "dtype": "bf16", "timing": kernel_timing,
+                            **{k: {"TFLOPs": round(g[0] / g[1] / 1e9, 1), "utilisation": round(g[0] / g[1] / 1e9 / MFMA_PEAK_TF, 4),
+                                   "launches_per_step": round(g[2] / (3 if use_graph else args.steps), 1),
+                                   "ms_per_step": round(g[1] / (3 if use_graph else args.steps), 3)}
+                               for k, g in mfma_groups.items() if g[1] > 0}}
         # where the step's GPU time goes, family by family, against the bound each family's declared work implies
         if family_kernels is not None:
             work = {}
@@ -820,11 +915,12 @@ def main():
         if args.config == 3:
             line["step_mfma_frac"] = round(STEP_FLOP / (ms * 1e-3) / 2.5e15, 4)      # 2.95 TFLOP per iteration / step time / dense bf16 peak
         line["config"]["cpu_affinity"] = "NUMA node %d of the GPU" % bound[0] if bound else "unbound"
-        line["config"]["gpu_clocks"] = clocks
+        if args.full:
+            line["config"]["gpu_clocks"] = clocks
         # optional kernel families in this run: the committed list, or the environment's for an A/B run
         line["config"]["switches"] = sorted(step.switches)
         line["config"]["switch_source"] = switch_source
-        side = world == 1 and not args.no_variants and not force_ddp
+        side = args.full and world == 1 and not args.no_variants and not force_ddp
         del step
         gc.collect()
         torch.cuda.empty_cache()
@@ -870,7 +966,7 @@ def main():
                 torch.distributed.destroy_process_group()
             except Exception as e:
                 line["rccl_1rank"] = {"value": None, "error": repr(e)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if bound:
                 os.sched_setaffinity(0, bound[1])                   # the CPU baseline's child process gets every core
             try:

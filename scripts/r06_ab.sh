@@ -17,7 +17,7 @@ for e in [x for x in sys.argv[1].split(",") if x]:
 print(" ".join([k + "=1" for k in sorted(names)] + extra))
 PY
 )
-  env $envs timeout 400 python bench.py --steps ${STEPS:-60} --warmup 10 --no-cpu-baseline --no-variants 2>$O/$name.err | tail -1 > $O/$name.json
+  env $envs timeout 400 python bench.py --full --steps ${STEPS:-60} --warmup 10 --no-cpu-baseline --no-variants 2>$O/$name.err | tail -1 > $O/$name.json
   python -c "import json; d=json.loads(open('$O/$name.json').read()); print('$name', d['value'], 'img/s', d['ms_per_step'], 'ms', 'loss', d.get('final_loss'), 'kernels', d.get('kernels_per_step'))" 2>/dev/null || { echo "$name FAILED"; tail -5 $O/$name.err; }
 }
 for rep in $(seq 1 ${REPS:-2}); do

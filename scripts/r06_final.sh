@@ -47,15 +47,15 @@ PY
 cat $O/errors.txt 2>/dev/null
 fi
 cd $R
-timeout 900 python bench.py 2>$O/bench.err | tail -1 > $O/bench.json
+timeout 900 python bench.py --full 2>$O/bench.err | tail -1 > $O/bench.json
 python -c "
 import json; d=json.load(open('$O/bench.json')); print({k: d[k] for k in ('value','ms_per_step','final_loss','kernels_per_step','step_mfma_frac')}, d['config']['launch']); print(d['roofline'])
 for k in ('fp32_path','eager_path','default_path','rccl_1rank','config2','config5'): print(k, {a: b for a, b in d.get(k, {}).items() if a in ('value','ms_per_step','error')})
 for r in d.get('families', []): print(r['name'], r['launches'], r['ms_per_step'], r.get('frac'))
 print({k: v for k, v in d.get('cpu_baseline', {}).items() if k in ('value','cores','kind','s_per_iter','note')})"
 tail -3 $O/bench.err
-cd /tmp; PYTHONPATH=$R MDETR_BENCH_FAMILIES=0 timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/trace_step -- python $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-variants > $O/bench_traced.json 2>$O/bench_traced.err
-cd $R; f=$(find /tmp/trace_step -name "*kernel_trace.csv" | head -1); st=$(find /tmp/trace_step -name "*kernel_stats.csv" | head -1)
+TS=${TMPDIR:-/tmp}/trace_step; cd "${TMPDIR:-/tmp}"; PYTHONPATH=$R MDETR_BENCH_FAMILIES=0 timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $TS -- python $R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-variants > $O/bench_traced.json 2>$O/bench_traced.err
+cd $R; f=$(find $TS -name "*kernel_trace.csv" | head -1); st=$(find $TS -name "*kernel_stats.csv" | head -1)
 # (eight of the TIMED replays: the last steps of the process are eagerly launched side measurements; MDETR_BENCH_FAMILIES=0: no second profiler inside the traced process)
 python -m monodetr_amd.tools.trace_stats $f --steps 8 --skip-last 14 --gaps 8 --out $O/${T}_bench_bf16_steady_kernel_stats.csv --top 14 > $O/trace_stats.txt 2>&1; grep -v " us/step " $O/trace_stats.txt | head -34 | cut -c1-170
 grep -E "mdetr|Name" $st | head -90 > $O/${T}_rocprofv3_stats_mdetr_kernels.csv

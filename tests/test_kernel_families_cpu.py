@@ -56,7 +56,7 @@ def test_committed_switch_list_is_the_configuration(monkeypatch):
 
 
 def test_bench_main_composes_its_json_line(monkeypatch, capsys):
-    """bench.main() from argument parsing to the JSON line with the GPU mocked away (a stand-in step, canned kernel
+    """bench.main() --full from argument parsing to the JSON line with the GPU mocked away (a stand-in step, canned kernel
     timings): catches slips in the line's bookkeeping -- committed switches, side measurements, roofline bytes following
     the operator's element types -- without a GPU."""
     import sys
@@ -103,7 +103,7 @@ def test_bench_main_composes_its_json_line(monkeypatch, capsys):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         del built[:]
-        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "2", "--warmup", "1", "--prime", "1", "--no-cpu-baseline"] + argv)
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "2", "--warmup", "1", "--prime", "1", "--no-cpu-baseline"] + argv)
         bench.main()
         line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
         assert line["metric"].startswith("training images/sec") and line["n_gpus"] == 1 and line["steps"] == 2 and line["value"] > 0
