@@ -326,7 +326,8 @@ int mdetr_adamw_step_counted(int param_dtype, void *param, float *master, const 
  * gradient of tensor i, same dtype and memory layout as its parameter; flat_offsets[i] / nbytes[i] (device, int64) = byte offset of
  * tensor i in `param` (x 2 in the fp32 arrays of a bf16 group: they are indexed by ELEMENT) and its size in bytes; a workgroup
  * takes up to chunk_bytes of one tensor: block_tensor / block_start (device) name tensor and byte start per workgroup,
- * tensor_block_begin (host, ntensors + 1) the first workgroup of every tensor -- the tables of mdetr_gather_flat.  Step size:
+ * tensor_block_begin (host, ntensors + 1) the first workgroup of every tensor -- the tables of mdetr_gather_flat; a tensor without
+ * workgroups (zero elements) is never read and its grad_ptrs[i] may be NULL.  Step size:
  * step_count_dev (as mdetr_adamw_step_counted) if not NULL, else step_size_dev if not NULL, else step_size. */
 int mdetr_adamw_step_gathered(int param_dtype, void *param, float *master, const void *const *grad_ptrs, int ntensors,
                               const int *tensor_block_begin, const int64_t *flat_offsets, const int64_t *nbytes, const int *block_tensor,

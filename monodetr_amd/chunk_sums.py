@@ -8,9 +8,26 @@ ONE launch of ``mdetr_chunk_sums`` for up to 48 gradients -- when the context cl
 result (the frozen-BN unfold of the backbone's weight gradients, monodetr/backbone.py).  The arithmetic is the same sum in the same
 order.  Outside the context every sum runs immediately.
 
-What makes the deferral safe: a weight gradient leaves its autograd function only towards the parameter's AccumulateGrad node,
-which stores the tensor without reading it (the iteration clears ``.grad`` to None first); the two readers inside the backward pass
-flush first.  Gradient exchange and optimizer run after the context has closed."""
+What makes the deferral safe -- the invariant, and who enforces it.  A registered result may be HELD but not READ before its flush.
+Autograd holds it: a weight gradient leaves its autograd function only towards the parameter's AccumulateGrad node, which stores
+the tensor without reading it -- provided the parameter has no ``.grad`` yet, carries no hook, and has the strides of the arriving
+gradient.  Everything else reads, and is closed in one of three ways:
+
+* the readers inside the product's own backward functions (the frozen-BN unfold, the decoder's concatenations, the fp32-bias
+  conversion of monodetr/linear.py) call ``flush()`` first;
+* ``deferred(module)`` -- the form ``TrainIteration._backward`` / ``_backward_backbone`` use -- asks ``reader_inside_backward``
+  before it opens: a DistributedDataParallel wrapper (its reducer copies every gradient into a bucket as it arrives), a parameter
+  with a tensor hook or a post-accumulate hook (``dist_helper.BucketedGradSync`` hangs one on every parameter), a parameter that
+  still has a ``.grad`` (AccumulateGrad adds into it) turn the deferral OFF for that backward pass: every sum is then launched at
+  once, as outside the context.  The second half of a cut backward pass (``held="verify"``) legitimately starts with the first
+  half's gradients in place; it defers, and raises afterwards if one of those was accumulated into;
+* ``conv_wgrad_ext.weight_gradient(..., like=weight)`` computes at once the gradient of a leaf weight whose strides differ from the
+  channels-last result's (AccumulateGrad would copy it into the parameter's layout).
+
+The flat and the two-part gradient exchange (``FlatGradSync``, ``SplitGradSync``) and the optimizer run after the context has closed.
+A bare ``deferred()`` checks nothing: the caller vouches for its consumers.  tests/test_deferred_sums_emulated_cpu.py holds the
+invariant for every consumer on the CPU emulation of the kernels, tests/test_grad_exchange_gpu.py for the exchanges of the whole
+model."""
 import ctypes
 import os
 import threading
@@ -58,14 +75,15 @@ def _launch(jobs):
         raise RuntimeError("mdetr_chunk_sums failed (code %d): %s" % (rc, msg.decode() if msg else "?"))
 
 
-def chunk_sum(part, out_dtype=torch.float32):
+def chunk_sum(part, out_dtype=torch.float32, defer=True):
     """part [chunks, cols] fp32 -> [cols] in out_dtype = the chunks added in order.  Inside ``deferred()`` the values arrive at the
-    next ``flush()``; `part` must then be a tensor of its own (not a shared scratch buffer): it is read later."""
+    next ``flush()``; `part` must then be a tensor of its own (not a shared scratch buffer): it is read later.  defer=False: this
+    sum now, whatever the context (its consumer reads it inside the backward pass)."""
     if not supported(part, out_dtype):
         raise RuntimeError("chunk_sum: needs contiguous fp32 partials [chunks, cols], cols a multiple of 4, 16-byte aligned")
     out = torch.empty(part.shape[1], dtype=out_dtype, device=part.device)
     with _lock:
-        if ENABLED and _depth > 0 and not IMMEDIATE:
+        if defer and ENABLED and _depth > 0 and not IMMEDIATE:
             if POISON:
                 out.fill_(float("nan"))
             _pending.append((part, out))
@@ -91,21 +109,59 @@ def flush():
             _launch(group)
 
 
+def reader_inside_backward(module=None, params=None, held="refuse"):
+    """Why the chunk sums of a backward pass into ``module``'s (or ``params``') parameters must NOT be deferred -- a short reason --,
+    or None: nothing that is visible from here reads a weight gradient before the flush.  held="verify": parameters that already
+    have a ``.grad`` are not a reason (``deferred`` checks afterwards that none of them was touched)."""
+    if module is not None:
+        from torch.nn.parallel import DistributedDataParallel
+        if isinstance(module, DistributedDataParallel):
+            return "DistributedDataParallel copies each gradient into its bucket during the backward pass"
+        if params is None:
+            params = module.parameters()
+    for p in params or ():
+        if not p.requires_grad:
+            continue
+        if p._backward_hooks or p._post_accumulate_grad_hooks:
+            return "a parameter carries a gradient hook"
+        if held == "refuse" and p.grad is not None:
+            return "a parameter still has a .grad: the new gradient is added to it during the backward pass"
+    return None
+
+
 class deferred:
-    """``with deferred(): loss.backward()`` -- chunk sums registered inside are computed together when the block ends (also when it
-    ends with an exception: no registered result stays unwritten)."""
+    """``with deferred(model): loss.backward()`` -- chunk sums registered inside are computed together when the block ends (also when
+    it ends with an exception: no registered result stays unwritten).  With ``module`` / ``params`` the block defers only if
+    ``reader_inside_backward`` finds no reason against it (``self.reason``); otherwise it changes nothing and every sum inside is
+    launched at once.  held="verify" (the second half of a cut backward pass): gradients that exist already must come out of the
+    block untouched -- a parameter that received gradient in both halves was accumulated from an unwritten sum, and that raises."""
+
+    def __init__(self, module=None, params=None, held="refuse"):
+        self.reason = None
+        self._held = ()
+        if (module is not None or params is not None) and ENABLED and not IMMEDIATE:       # (nothing is deferred otherwise: nothing to ask)
+            params = list(module.parameters() if params is None else params)
+            self.reason = reader_inside_backward(module, params, held)
+            if self.reason is None and held == "verify":
+                self._held = [(p, p.grad, p.grad._version) for p in params if p.requires_grad and p.grad is not None]
 
     def __enter__(self):
         global _depth
-        with _lock:
-            _depth += 1
+        if self.reason is None:
+            with _lock:
+                _depth += 1
         return self
 
     def __exit__(self, *exc):
         global _depth
+        if self.reason is not None:
+            return False
         with _lock:
             _depth -= 1
             last = _depth == 0
         if last:
             flush()
+        if exc[0] is None and any(p.grad is not g or g._version != v for p, g, v in self._held):
+            raise RuntimeError("chunk_sums.deferred(held='verify'): a parameter that had a gradient before this backward pass received "
+                               "another one inside it -- it was added from a sum that was not computed yet")
         return False

@@ -100,7 +100,7 @@ class _Conv3x3(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             from . import conv_wgrad_ext
             if conv_wgrad_ext.supported(x, dy, 3, 1):                    # csrc/conv_wgrad.hip: split-K over pixel tiles on the matrix cores
-                dw = conv_wgrad_ext.weight_gradient(x, dy, 3, 1, weight.dtype)
+                dw = conv_wgrad_ext.weight_gradient(x, dy, 3, 1, weight.dtype, like=weight)
             else:
                 dw = torch.ops.aten.convolution_backward(dy, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, (False, True, False))[1]
         ds = None

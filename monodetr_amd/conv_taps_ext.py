@@ -145,7 +145,7 @@ class _ConvStrided(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             from . import conv_wgrad_ext
             if conv_wgrad_ext.supported(x, dy, k, 2):
-                dw = conv_wgrad_ext.weight_gradient(x, dy, k, 2, weight.dtype)
+                dw = conv_wgrad_ext.weight_gradient(x, dy, k, 2, weight.dtype, like=weight)
             else:
                 dw = torch.ops.aten.convolution_backward(dy, x, weight, None, (2, 2), pad, (1, 1), False, (0, 0), 1, (False, True, False))[1]
         if ctx.shift_dtype is not None and ctx.needs_input_grad[2]:

@@ -31,6 +31,15 @@ def supported(x, dy, k, stride):
 TOKEN_ROUTE = True
 
 
+def _chunk_sum_route(chunk_sums, cuda, cols, dtype):
+    """Do the partials go to chunk_sums.chunk_sum (which defers or launches at once)?  On the GPU inside ``deferred()`` only -- outside it
+    the column-sum kernel adds them out of the shared workspace; with the emulated kernel (tests) whenever the family is on, so that
+    the sums of a backward pass that may not defer still run the kernel."""
+    if cols % 4 != 0 or dtype not in (torch.float32, torch.bfloat16):
+        return False
+    return chunk_sums.deferring() if cuda and chunk_sums._backend is None else chunk_sums._backend is not None and chunk_sums.ENABLED
+
+
 def token_weight_gradient(x2, dy2, dtype, bias=False):
     """(dW [N, K], db [N] or None) = (dy2^T x2, column sums of dy2) for token matrices x2 [T, K], dy2 [T, N] (bf16, contiguous rows, T a
     multiple of 8): the 1x1 case of the convolution weight-gradient kernel, the bias gradient riding along on the dy operand that
@@ -45,7 +54,7 @@ def token_weight_gradient(x2, dy2, dtype, bias=False):
     cols = N * K + (N if bias else 0)
     cuda = x2.is_cuda
     from . import chunk_sums
-    batched = chunk_sums.deferring() and cols % 4 == 0 and dtype in (torch.float32, torch.bfloat16) and (cuda or chunk_sums._backend is not None)
+    batched = _chunk_sum_route(chunk_sums, cuda, cols, dtype)
     if cuda and _backend is None and not batched:
         from . import _workspace as W_
         part = W_.get("conv_wgrad", x2.device, chunks * cols * 4).view(torch.float32)[:chunks * cols]
@@ -82,8 +91,18 @@ def token_supported(x2, dy2):
     return ok and x2.shape[1] % 8 == 0 and dy2.shape[1] % 8 == 0
 
 
-def weight_gradient(x, dy, k, stride, dtype=torch.bfloat16):
-    """x [B, C, H, W], dy [B, N, OH, OW] (channels_last bf16) -> dW [N, C, k, k] in ``dtype`` (channels_last strides)."""
+def _stolen(like, N, C, k):
+    """Does AccumulateGrad keep a [N, C, k, k] gradient with channels_last strides for the leaf ``like`` as it is (same strides wherever a
+    dimension is longer than 1)?  Otherwise it copies the gradient into the parameter's layout -- it READS it inside the backward pass."""
+    if like is None or not like.is_leaf:
+        return True                                  # (an intermediate -- a folded weight --: its consumer flushes before it reads)
+    want = (k * k * C, 1, k * C, C)
+    return tuple(like.shape) == (N, C, k, k) and all(n == 1 or a == b for n, a, b in zip(like.shape, like.stride(), want))
+
+
+def weight_gradient(x, dy, k, stride, dtype=torch.bfloat16, like=None):
+    """x [B, C, H, W], dy [B, N, OH, OW] (channels_last bf16) -> dW [N, C, k, k] in ``dtype`` (channels_last strides).
+    like: the weight the gradient is for; a leaf whose strides are not the result's gets its sum at once, never deferred (chunk_sums.py)."""
     B, C, H, W = x.shape
     _, N, OH, OW = dy.shape
     lib = _lib()
@@ -93,7 +112,7 @@ def weight_gradient(x, dy, k, stride, dtype=torch.bfloat16):
     cols = N * k * k * C
     cuda = x.is_cuda
     from . import chunk_sums
-    batched = chunk_sums.deferring() and dtype in (torch.float32, torch.bfloat16) and (cuda or chunk_sums._backend is not None)
+    batched = _chunk_sum_route(chunk_sums, cuda, cols, dtype)
     if cuda and _backend is None and not batched:
         from . import _workspace as W_
         part = W_.get("conv_wgrad", x.device, chunks * cols * 4).view(torch.float32)[:chunks * cols]
@@ -105,7 +124,7 @@ def weight_gradient(x, dy, k, stride, dtype=torch.bfloat16):
         _capi.check(rc, "mdetr_conv_wgrad")
     part = part.view(chunks, cols)
     if batched:
-        dw = chunk_sums.chunk_sum(part, dtype)
+        dw = chunk_sums.chunk_sum(part, dtype, defer=_stolen(like, N, C, k))
     elif cuda and _backend is None:
         from .colsum_ext import column_sum, supported as colsum_ok
         out_dt = dtype if dtype in (torch.float32, torch.bfloat16) else torch.float32

@@ -501,7 +501,9 @@ int mdetr_adamw_step_gathered(int param_dtype, void *param, float *master, const
     if (!aligned16(param) || !aligned16(master) || !aligned16(exp_avg) || !aligned16(exp_avg_sq))
         return fail(MDETR_E_ALIGN, "mdetr_adamw_step_gathered: buffers must be 16-byte aligned");
     for (int i = 0; i < ntensors; ++i)
-        if (!grad_ptrs[i] || tensor_block_begin[i + 1] < tensor_block_begin[i] || (reinterpret_cast<uintptr_t>(grad_ptrs[i]) & (esz - 1)))
+        // (a tensor without blocks -- zero elements -- is never read: its gradient's address may be null)
+        if ((!grad_ptrs[i] && tensor_block_begin[i + 1] != tensor_block_begin[i]) || tensor_block_begin[i + 1] < tensor_block_begin[i] ||
+            (reinterpret_cast<uintptr_t>(grad_ptrs[i]) & (esz - 1)))
             return fail(MDETR_E_ARG, "mdetr_adamw_step_gathered: tensor %d: null / misaligned gradient or decreasing block table", i);
     DeviceScope dev(device);
     if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "mdetr_adamw_step_gathered: set device %d: %s", device, hipGetErrorString(dev.err));

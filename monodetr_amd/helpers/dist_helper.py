@@ -243,7 +243,11 @@ class BucketedGradSync:
 
     When to prefer which: on ONE node the flat exchange costs 8 launches and ~1-2 ms of un-overlapped xGMI time at the end
     of a ~30 ms step; this form hides that time at the price of one Python hook per parameter (345) and ~3 launches per
-    bucket.  ``bench.py`` selects with MDETR_BENCH_SYNC=flat|bucketed|ddp."""
+    bucket.  ``bench.py`` selects with MDETR_BENCH_SYNC=flat|bucketed|ddp.
+
+    The hooks READ ``p.grad`` inside the backward pass, so the chunk sums of the split weight-gradient kernels cannot be deferred to
+    its end (chunk_sums.py): ``chunk_sums.deferred`` sees the hooks on the parameters and launches every sum at once for this
+    exchange -- ~160 small launches more per iteration than the flat forms; acceptable for a form that only runs eagerly."""
 
     def __init__(self, params, world_size=None, group=None, bucket_mb=32.0):
         self.params = [p for p in params if p.requires_grad]

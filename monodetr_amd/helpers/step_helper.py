@@ -174,20 +174,22 @@ class TrainIteration:
         self._backward(total)
         return total
 
-    @staticmethod
-    def _backward(total):
-        """loss.backward() with the chunk sums of the split weight-gradient kernels batched into one launch (chunk_sums.py)."""
+    def _backward(self, total):
+        """loss.backward() with the chunk sums of the split weight-gradient kernels batched into one launch (chunk_sums.py) -- unless
+        something would read a gradient inside the backward pass: the DistributedDataParallel wrapper, a parameter with a hook
+        (BucketedGradSync), a retained .grad.  ``chunk_sums.deferred`` decides, per backward pass."""
         from .. import chunk_sums
-        with chunk_sums.deferred():
+        with chunk_sums.deferred(self.model, list(self.raw_model.parameters())):
             total.backward()
 
     def _backward_backbone(self):
-        """The second part of a cut backward pass: from the gradients that arrived at the pyramid levels down through the backbone."""
+        """The second part of a cut backward pass: from the gradients that arrived at the pyramid levels down through the backbone.
+        (held="verify": the first part's gradients are in place; none of them may receive a second contribution here.)"""
         pairs = [(t, td.grad) for t, td in (self._boundary or ()) if td.grad is not None]
         self._boundary = None
         if pairs:
             from .. import chunk_sums
-            with chunk_sums.deferred():
+            with chunk_sums.deferred(self.model, list(self.raw_model.parameters()), held="verify"):
                 torch.autograd.backward([t for t, _ in pairs], [g for _, g in pairs])
 
     def _with_grad(self, exclude=()):

@@ -138,6 +138,29 @@ def _worker(rank, world, port, out_dir, port2):
             worst_bucketed = max(worst_bucketed, max(((got3[n] - avg[n]).abs().max() / (avg[n].abs().max() + 1e-12)).item() for n in avg))
             n_buckets = len(bsync.buckets)
 
+        # the exchanges with the kernels behind them: the emulated stack of tests/deferred_stack.py (split weight-gradient kernels on the
+        # CPU shim, chunk sums DEFERRED and poisoned until their flush) through TrainIteration, a different shard per rank, three
+        # iterations -- every rank ends with the average of the per-rank gradients computed with every sum at once and no exchange
+        import deferred_stack as ds
+        local_st, _, _ = ds.run_case("none", "immediate", seed0=40 + 10 * rank)
+        emulated = {}
+        for kind in ("bucketed", "flat", "split"):
+            got_st, seen_st, _ = ds.run_case(kind, "deferred", seed0=40 + 10 * rank)
+            worst_st, same_st, finite_st = 0.0, True, True
+            for it_ in range(3):
+                for n in sorted(local_st[it_]):
+                    want = local_st[it_][n].clone()
+                    dist.all_reduce(want)
+                    want = want / world
+                    g = got_st[it_][n]
+                    finite_st = finite_st and bool(torch.isfinite(g.float()).all())
+                    worst_st = max(worst_st, ((g.float() - want.float()).abs().max() / (want.float().abs().max() + 1e-12)).item())
+                    gs = [torch.empty_like(g) for _ in range(world)]
+                    dist.all_gather(gs, g.contiguous())
+                    same_st = same_st and all(torch.equal(gs[0], x) for x in gs[1:])
+            emulated[kind] = dict(worst=worst_st, same=same_st, finite=finite_st, n=len(got_st[0]),
+                                  sums=[(s_["registered"], s_["launches"]) for s_ in seen_st])
+
         # bench.py's own step object on the N > 1 path (gloo here, RCCL on the GPUs), both exchanges: ranks hold identical
         # parameters after two iterations, and every rank runs the same committed switch list
         import bench
@@ -175,7 +198,7 @@ def _worker(rank, world, port, out_dir, port2):
         same_switches = all(l == lists[0] for l in lists)
         torch.save(dict(worst=worst, same=same, unused=unused, n_grads=len(got), worst_flat=worst_flat, same_flat=same_flat,
                         mixed_ok=mixed_ok, static_ok=static_ok, worst_bucketed=worst_bucketed, n_buckets=n_buckets, same_bench=same_bench,
-                        same_switches=same_switches, overlap_vs_flat=overlap_vs_flat, split_kind=split_kind), os.path.join(out_dir, "r%d.pt" % rank))
+                        same_switches=same_switches, overlap_vs_flat=overlap_vs_flat, split_kind=split_kind, emulated=emulated), os.path.join(out_dir, "r%d.pt" % rank))
     finally:
         dist.destroy_process_group()
 
@@ -193,6 +216,12 @@ def test_two_rank_ddp_step_matches_manual_gradient_average(tmp_path):
         assert res["same_bench"] == {"flat": True, "bucketed": True, "overlap": True, "deferred": True} and res["same_switches"], res
         assert res["split_kind"] == "SplitGradSync" and res["overlap_vs_flat"] < 1e-6, res
         assert res["n_grads"] > 300
+        for kind, e in res["emulated"].items():
+            assert e["finite"] and e["same"] and e["worst"] < 1e-4 and e["n"] == 10, (kind, e)
+        # the flat and the two-part exchange read after the flush: five registered sums per iteration, in one / two multi-job launches;
+        # the bucketed one reads from hooks inside the backward pass: nothing registered, five single launches
+        assert res["emulated"]["flat"]["sums"] == [(5, [5])] * 3 and res["emulated"]["split"]["sums"] == [(5, [3, 2])] * 3
+        assert res["emulated"]["bucketed"]["sums"] == [(0, [1] * 5)] * 3
         assert all(n.startswith("label_enc") or ".sa_v_proj." in n or "decoder.query_scale" in n or "decoder.ref_point_head" in n
                    for n in res["unused"]), res["unused"]
 

@@ -225,3 +225,35 @@ def test_gathered_update_reads_gradient_slices_at_any_offset():
     for x, y in zip(pa, pb):
         tol = 1e-6 if x.dtype == torch.float32 else 1e-2
         assert (x.detach().float() - y.detach().float()).abs().max() <= tol * max(1.0, x.detach().float().abs().max().item())
+
+
+def test_gathered_update_takes_a_parameter_without_elements():
+    """A zero-element parameter among ordinary ones (its gradient's address is null): the gathered AdamW (csrc/adamw.hip and its C-ABI
+    entry on the CPU shim) leaves the empty one alone, as the multi-tensor path does, and steps the others
+    * as torch.optim.AdamW does on fp64 copies, without weight decay -- there the reference's formula (eps added before the bias
+      correction, decay scaled by the corrected step) and torch's coincide to ~1e-9 --, and
+    * as this module's AdamW (the mirror pinned to the reference's recorded steps) does on fp64 copies, with weight decay;
+    fp32 arithmetic against fp64: 2e-6 relative, the bar of test_fused_adamw_matches_reference_steps_fp32."""
+    from monodetr_amd.helpers.optimizer_helper import AdamW
+    shapes = [(40, 7), (0,), (130,), (3, 0, 5), (9,)]
+    for decay, reference in ((0.0, torch.optim.AdamW), (1e-2, AdamW)):
+        torch.manual_seed(4)
+        ps = [torch.nn.Parameter(torch.randn(s)) for s in shapes]
+        refs = [torch.nn.Parameter(p.detach().double().clone()) for p in ps]
+        start = [r.detach().clone() for r in refs]
+        opt = _fused([{'params': ps, 'weight_decay': decay}], "emul", lr=1e-3)
+        ref = reference([{'params': refs, 'weight_decay': decay}], lr=1e-3)
+        assert opt._gather
+        for step in range(3):
+            gen = torch.Generator().manual_seed(70 + step)
+            for p, r in zip(ps, refs):
+                p.grad = torch.randn(p.shape, generator=gen)
+                r.grad = p.grad.double()
+            assert ps[1].grad.data_ptr() == 0                          # what the entry point is handed for the empty tensor
+            opt.step(); ref.step()
+        assert any(b.get('gather') is not None for b in opt._flat[1])  # the gathered form ran
+        for p, r, s, r0 in zip(ps, refs, shapes, start):
+            assert p.shape == r.shape == torch.Size(s)
+            if p.numel():
+                assert (p.detach().double() - r.detach()).abs().max() <= 2e-6 * max(1.0, r.detach().abs().max().item()), (decay, s)
+                assert (r.detach() - r0).abs().max() > 1e-3            # (three steps of ~lr each: the bar is a thousandth of the movement)
