@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MDETR_ABI_VERSION 12
+#define MDETR_ABI_VERSION 13
 
 /* element types of the floating-point tensors */
 #define MDETR_F32 0
@@ -370,6 +370,20 @@ int mdetr_tgemm(const void *a, const void *w, const void *bias, const void *res,
  */
 int mdetr_tgemm_masked(const void *a, const void *w, const void *res, const void *mask, void *y, int64_t T, int N, int K,
                        int64_t lda, int64_t ldw, int64_t ldr, int64_t ldm, int64_t ldy, int device, void *stream);
+/*
+ * The same two products with EVERY tensor in fp32 (ABI 13): a, w, bias, res, mask, y.  Each operand element is split once into three
+ * bf16 parts (hi + mid + lo) and a product is six bf16 matrix-instruction terms accumulated in fp32: the accuracy of an
+ * fp32-accumulated fp32 product (the dropped terms are below 2^-24 of |a||w| per product).  Same argument order, same tail, same
+ * dropout decisions (hash, element index t N + n, scale) as the bf16 pair.  flags: MDETR_TGEMM_RELU, MDETR_TGEMM_NN;
+ * MDETR_TGEMM_BIAS_F32 / MDETR_TGEMM_OUT_F32 are implied (accepted and ignored); any other bit is an error.
+ * Shape rules: K % 8 == 0, N % 8 == 0, row strides % 4 == 0 and >= the row length, 16-byte aligned pointers, every tensor below
+ * 2^31 bytes.  An infinite operand yields NaN (x - bf16(x) is NaN for +-inf) where a library GEMM yields +-inf.
+ */
+int mdetr_tgemm_f32(const void *a, const void *w, const void *bias, const void *res, void *y, int64_t T, int N, int K,
+                    int64_t lda, int64_t ldw, int64_t ldr, int64_t ldy, int flags, float dropout_p, uint64_t seed,
+                    const void *seed_dev, int device, void *stream);
+int mdetr_tgemm_f32_masked(const void *a, const void *w, const void *res, const void *mask, void *y, int64_t T, int N, int K,
+                           int64_t lda, int64_t ldw, int64_t ldr, int64_t ldm, int64_t ldy, int device, void *stream);
 
 /*
  * Grouped fp32 products on the f32-input matrix instruction (ABI 9; csrc/sgemm.hip): up to MDETR_SGEMM_MAX_PROBLEMS independent

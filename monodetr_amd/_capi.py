@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MDETR_LIB_PATH") or os.path.join(_HERE, "libmonodetr_amd.so")
 
 MDETR_F32, MDETR_F64, MDETR_BF16 = 0, 1, 2
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _c_int, _c_vp = ctypes.c_int, ctypes.c_void_p
 
@@ -50,6 +50,8 @@ SIGNATURES = {
     "mdetr_sgemm_workspace_bytes": (ctypes.c_int64, [_c_int, _c_vp, _c_int]),
     "mdetr_sgemm_grouped": (_c_int, [_c_int, _c_vp, _c_int, _c_vp, ctypes.c_int64, _c_int, _c_vp]),
     "mdetr_tgemm_masked": (_c_int, [_c_vp] * 5 + [ctypes.c_int64, _c_int, _c_int] + [ctypes.c_int64] * 5 + [_c_int, _c_vp]),
+    "mdetr_tgemm_f32": (_c_int, [_c_vp] * 5 + [ctypes.c_int64, _c_int, _c_int] + [ctypes.c_int64] * 4 + [_c_int, ctypes.c_float, ctypes.c_uint64, _c_vp, _c_int, _c_vp]),
+    "mdetr_tgemm_f32_masked": (_c_int, [_c_vp] * 5 + [ctypes.c_int64, _c_int, _c_int] + [ctypes.c_int64] * 5 + [_c_int, _c_vp]),
     "mdetr_column_sum_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, _c_int]),
     "mdetr_column_sum": (_c_int, [_c_int, _c_vp, _c_vp, _c_vp, ctypes.c_int64, ctypes.c_int64, _c_int, ctypes.c_int64, _c_int, _c_vp]),
     "mdetr_box_refine": (_c_int, [_c_vp] * 3 + [ctypes.c_int64, _c_int, _c_int, _c_vp]),

@@ -23,6 +23,7 @@ struct TgemmProblem {
     const uint64_t *seed_dev; // added to seed when not null (a replayed graph's seed lives on the device)
     const void *mask = nullptr;   // bf16 [T, N] (row stride ldm) or null: y = mask <= 0 ? 0 : a w + res (NN form, bf16 output, no other tail)
     int64_t ldm = 0;
+    bool f32 = false;             // every tensor (a, w, bias, res, mask, y) is fp32: the three-way bf16 split form (flags: kTgemmRelu | kTgemmNN only)
 };
 
 bool tgemm_supported(const TgemmProblem &p);

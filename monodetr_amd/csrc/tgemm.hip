@@ -21,6 +21,8 @@
 // Workgroup ids go round-robin over the 8 XCDs; the column tiles of one token range are ids 8 apart (same XCD, adjacent
 // dispatch slots), so the second reader of an input tile finds it in that XCD's L2.
 // Algorithmic bytes = 2 (T K + T N [+ T N residual]) + 2 N K; flops = 2 T N K.
+// The fp32 form of the same product (every tensor fp32, operands split three ways into bf16 on their way into LDS) is the sibling
+// kernel tgemm32_kernel further down: see the comment above it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -476,10 +478,443 @@ hipError_t launch_tail(const TgemmArgs &g, int bm, int bn, hipStream_t st)
     return g.res ? launch_any<NN, PF, 1>(g, bm, bn, st) : launch_any<NN, PF, 0>(g, bm, bn, st);
 }
 
+
+// ================================================================================================================================
+// The fp32 form (mdetr_tgemm_f32 / mdetr_tgemm_f32_masked): the same product with fp32 a, w, bias, res, mask and y, on the SAME
+// matrix instruction.  Each fp32 element is split ONCE, on its way from the staging registers into LDS, into three bf16 parts
+//     hi = bf16(x),  mid = bf16(x - hi),  lo = bf16(x - hi - mid)            (both subtractions exact: attn.hip's split_bf16)
+// kept as three bf16 planes per operand; a product step issues the six terms lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi (small terms
+// first) into the same fp32 accumulators: every partial product is exact in fp32 and what is dropped (mid.lo, lo.mid, lo.lo) is
+// below 2^-24 of |a||w| per product.  The f32-input MFMA runs at 1/16 of the bf16 rate: 2.7x the cost of the six terms.
+// Non-finite operands: x - bf16(x) is NaN for +-inf, so an infinite input yields NaN where the library yields +-inf (attn.hip's
+// fp32 mode does the same); no fix-up pass.
+// Kept from the bf16 form: buffer-resource loads (out-of-range lanes read zero), register-staged slabs, persistent workgroups in
+// multiples of 8 with the XCD-aware tile order, park-in-LDS / whole-row drain with straight-line tails.  Re-chosen: the slab is 32
+// contraction values for the 64 x 64 tile and 16 for 128 x 64 / 128 x 128 (2 buffers x 3 planes x (BM + BN) rows of BK + 8 bf16: 60 / 54 /
+// 72 KB, two workgroups per CU; rows of 20 / 12 dwords keep the 16 rows of a ds_read_b128 lane group on distinct bank quads); every
+// fragment read feeds two or three MFMAs (6 reads per 6 MFMAs on 64 x 64, 9 per 12 on 128 x 64, 12 per 24 on 128 x 128); the residual
+// and mask tiles (fp32: twice the registers) are requested batch by batch inside the drain, after the accumulators are parked.
+// The NN weight needs no shuffle: a thread loads 4 k-rows x 4 columns and writes each column's 4 k values (8 bytes per plane).
+// Algorithmic bytes = 4 (T K + T N [+ T N residual] [+ T N mask]) + 4 N K; flops = 2 T N K (the six terms are an implementation cost).
+struct Tgemm32Args {
+    const float *a, *w, *res, *mask, *bias;
+    float *y;
+    int64_t T, lda, ldw, ldr, ldy, ldm;
+    int N, K, gx, ny, flags, tiles_m;
+    uint32_t thresh;
+    float keep_scale;
+    uint64_t seed;
+    const uint64_t *seed_dev;
+};
+
+template <int BM, int BN, int BK>
+constexpr size_t tgemm32_lds()
+{
+    constexpr size_t slabs = static_cast<size_t>(2) * 3 * (BM + BN) * (BK + 8) * 2, tile = static_cast<size_t>(BM) * (BN + kCPad) * 4;
+    return slabs > tile ? slabs : tile;
+}
+
+// 4 fp32 values (the 16 bytes of a staged piece, or 4 gathered values) -> their hi / mid / lo bf16 parts, 8 bytes each
+__device__ __forceinline__ void split4(const float (&x)[4], bf16x4 &h, bf16x4 &m, bf16x4 &l)
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const __bf16 hi = static_cast<__bf16>(x[i]);
+        const float r1 = x[i] - static_cast<float>(hi);               // exact
+        const __bf16 mi = static_cast<__bf16>(r1);
+        h[i] = hi; m[i] = mi; l[i] = static_cast<__bf16>(r1 - static_cast<float>(mi));     // exact again; <= 8 significant bits are left
+    }
+}
+
+// BK: contraction values per slab;  PF: register sets as in tgemm_kernel;  MASK: the masked tail (NN only)
+template <int BM, int BN, int BK, bool NN, int PF, bool MASK>
+__global__ __launch_bounds__(256, 2)
+void tgemm32_kernel(const Tgemm32Args g)
+{
+    constexpr int LD = BK + 8;                                   // LDS row of a plane (bf16)
+    constexpr int QK = BK / 4;                                   // 16-byte pieces (4 fp32) of a slab row
+    constexpr int TM = BM / 64, TN = BN / 64;                    // 32 x 32 blocks of a wave (waves 2 x 2)
+    constexpr int XCH = BM * QK / kThreadsT;                     // pieces of an input slab per thread
+    constexpr int WCH = NN ? 4 : BN * QK / kThreadsT;            // weight slab: pieces per thread (NT) / the 4 k-rows of one 4 x 4 block (NN)
+    constexpr int WTHR = NN ? QK * (BN / 4) : kThreadsT;         // threads that stage the weight slab
+    static_assert(TM >= 1 && TN >= 1 && XCH >= 1 && WCH >= 1 && WTHR <= kThreadsT && kThreadsT % QK == 0 && BK % 16 == 0, "tile / workgroup shape");
+    MDETR_DYNAMIC_LDS(unsigned char, tg_smem);
+    __bf16 *Xs = reinterpret_cast<__bf16 *>(tg_smem);            // [2][3][BM][LD]  (buffer, plane hi / mid / lo)
+    __bf16 *Ws = Xs + 2 * 3 * BM * LD;                           // [2][3][BN][LD]
+    float *Cs = reinterpret_cast<float *>(tg_smem);              // [BM][BN + kCPad], after a tile's last slab
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
+    const int wm = wave & 1, wn = wave >> 1;
+    const int KT = (g.K + BK - 1) / BK;
+    const int G = gridDim.x, vtiles = g.gx * g.ny;
+    const int tiles_m = g.tiles_m;
+    auto tile_of = [&](int v, int &col, int64_t &m0) __attribute__((always_inline)) {
+        const int grp = v >> 3;
+        col = grp % g.ny;
+        m0 = (static_cast<int64_t>(grp / g.ny) * 8 + (v & 7)) * BM;
+    };
+    auto next_tile = [&](int v) __attribute__((always_inline)) {
+        for (; v < vtiles; v += G) {
+            if ((v >> 3) / g.ny * 8 + (v & 7) < tiles_m) break;
+        }
+        return v;
+    };
+
+    const unsigned a_bytes = static_cast<unsigned>(((g.T - 1) * g.lda + g.K) * 4);                 // (T lda < 2^29: tgemm_supported)
+    const unsigned w_bytes = static_cast<unsigned>(NN ? ((static_cast<int64_t>(g.K) - 1) * g.ldw + g.N) * 4 : ((static_cast<int64_t>(g.N) - 1) * g.ldw + g.K) * 4);
+    const mdetr_rsrc ar = make_rsrc(g.a, a_bytes), wr_ = make_rsrc(g.w, w_bytes);
+    const int xq = tid % QK, xk = xq * 4;                        // NT maps: this thread's piece / k offset inside a slab row (the same for all its pieces)
+    const int wkg = tid % QK, wnb = tid / QK;                    // NN map: k-group (4 rows) and column block (4 columns) of this thread
+    unsigned xoff[XCH], woff[NN ? 1 : WCH];
+    int xdst[XCH], wdst[NN ? 1 : WCH];
+#pragma unroll
+    for (int j = 0; j < XCH; ++j) xdst[j] = ((tid + kThreadsT * j) / QK) * LD + xk;
+    if (NN) {
+        wdst[0] = wnb * 4 * LD + wkg * 4;
+    } else {
+#pragma unroll
+        for (int j = 0; j < (NN ? 1 : WCH); ++j) wdst[j] = ((tid + kThreadsT * j) / QK) * LD + xk;
+    }
+    auto aim = [&](int v) __attribute__((always_inline)) {
+        int col; int64_t m0;
+        tile_of(v, col, m0);
+        const int n0 = col * BN;
+#pragma unroll
+        for (int j = 0; j < XCH; ++j) {
+            const int64_t t = m0 + (tid + kThreadsT * j) / QK;
+            xoff[j] = t < g.T ? (static_cast<unsigned>(t) * static_cast<unsigned>(g.lda) + xk) * 4u : kRsrcOob;
+        }
+        if (NN) {
+            woff[0] = (tid < WTHR && n0 + wnb * 4 < g.N) ? static_cast<unsigned>((static_cast<int64_t>(wkg * 4) * g.ldw + n0 + wnb * 4) * 4) : kRsrcOob;
+        } else {
+#pragma unroll
+            for (int j = 0; j < (NN ? 1 : WCH); ++j) {
+                const int row = n0 + (tid + kThreadsT * j) / QK;
+                woff[j] = row < g.N ? (static_cast<unsigned>(row) * static_cast<unsigned>(g.ldw) + xk) * 4u : kRsrcOob;
+            }
+        }
+    };
+
+    bf16x8 xr[PF][XCH], wr[PF][WCH];                             // 16 bytes = 4 fp32 each (the load moves bits)
+    auto fetch = [&](int kt, bf16x8 (&xs_)[XCH], bf16x8 (&ws_)[WCH]) __attribute__((always_inline)) {
+        const int k0 = kt * BK;
+        const bool xin = k0 + xk < g.K;                          // (K % 8 == 0: a piece of 4 is whole or dead)
+#pragma unroll
+        for (int j = 0; j < XCH; ++j) xs_[j] = rsrc_load_bf16x8(ar, xin ? xoff[j] : kRsrcOob, static_cast<unsigned>(k0 * 4));
+        if (NN) {
+            if (tid < WTHR) {
+                const bool kin = k0 + wkg * 4 < g.K;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    ws_[i] = rsrc_load_bf16x8(wr_, kin ? woff[0] : kRsrcOob, static_cast<unsigned>((static_cast<int64_t>(k0 + i) * g.ldw) * 4));
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < WCH; ++j) ws_[j] = rsrc_load_bf16x8(wr_, xin ? woff[NN ? 0 : j] : kRsrcOob, static_cast<unsigned>(k0 * 4));
+        }
+    };
+    auto put3 = [&](__bf16 *plane0, int rows, int dst, const float (&x)[4]) __attribute__((always_inline)) {
+        bf16x4 h, m, l;
+        split4(x, h, m, l);
+        *reinterpret_cast<bf16x4 *>(plane0 + dst) = h;
+        *reinterpret_cast<bf16x4 *>(plane0 + rows * LD + dst) = m;
+        *reinterpret_cast<bf16x4 *>(plane0 + 2 * rows * LD + dst) = l;
+    };
+    auto deposit = [&](int buf, const bf16x8 (&xs_)[XCH], const bf16x8 (&ws_)[WCH]) __attribute__((always_inline)) {
+        __bf16 *xb = Xs + buf * 3 * BM * LD, *wb = Ws + buf * 3 * BN * LD;
+#pragma unroll
+        for (int j = 0; j < XCH; ++j) {
+            float x[4];
+            __builtin_memcpy(x, &xs_[j], 16);
+            put3(xb, BM, xdst[j], x);
+        }
+        if (NN) {
+            if (tid < WTHR) {
+                float in[4][4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) __builtin_memcpy(in[i], &ws_[i], 16);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {                    // column q of the 4 x 4 block: its 4 k values
+                    const float x[4] = {in[0][q], in[1][q], in[2][q], in[3][q]};
+                    put3(wb, BN, wdst[0] + q * LD, x);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < WCH; ++j) {
+                float x[4];
+                __builtin_memcpy(x, &ws_[j], 16);
+                put3(wb, BN, wdst[NN ? 0 : j], x);
+            }
+        }
+    };
+
+    f32x16 acc[TN][TM];
+    auto clear = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int a_ = 0; a_ < TN; ++a_)
+#pragma unroll
+            for (int b_ = 0; b_ < TM; ++b_)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[a_][b_][i] = 0.f;
+    };
+    auto products = [&](int buf) __attribute__((always_inline)) {
+        const __bf16 *xl = Xs + (buf * 3 * BM + wm * (BM / 2) + l31) * LD + half * 8;     // + BM LD per plane, + 32 LD per block, + 16 per k-step
+        const __bf16 *wl = Ws + (buf * 3 * BN + wn * (BN / 2) + l31) * LD + half * 8;
+#pragma unroll
+        for (int ks = 0; ks < BK / 16; ++ks) {
+            bf16x8 xf[3][TM], wf[3][TN];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+#pragma unroll
+                for (int b_ = 0; b_ < TM; ++b_) xf[p][b_] = *reinterpret_cast<const bf16x8 *>(xl + (p * BM + b_ * 32) * LD + ks * 16);
+#pragma unroll
+                for (int a_ = 0; a_ < TN; ++a_) wf[p][a_] = *reinterpret_cast<const bf16x8 *>(wl + (p * BN + a_ * 32) * LD + ks * 16);
+            }
+            // the six terms, small ones first, term by term over the wave's blocks (consecutive MFMAs write different accumulators)
+            constexpr int term_w[6] = {2, 0, 1, 1, 0, 0}, term_x[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+            for (int t = 0; t < 6; ++t)
+#pragma unroll
+                for (int a_ = 0; a_ < TN; ++a_)
+#pragma unroll
+                    for (int b_ = 0; b_ < TM; ++b_) acc[a_][b_] = mfma_bf16(wf[term_w[t]][a_], xf[term_x[t]][b_], acc[a_][b_]);     // D^T[n][token]
+        }
+    };
+
+    // ---- a tile's tail: piece c = tid + 256 j of the output tile = row c / (BN / 8), 8 features at 8 (c % (BN / 8)), as in tgemm_kernel
+    constexpr int PR = BN / 8, NP = BM * PR / kThreadsT;
+    constexpr int NPB = NP < 2 ? NP : 2;                         // pieces per batch of the drain (8 fp32 each of tile, residual, mask)
+    const int pc = tid % PR;
+    const float lo = (g.flags & kTgemmRelu) ? 0.f : -__builtin_inff();
+    const bool has_res = g.res != nullptr;
+    const uint64_t sd = g.thresh ? g.seed + (g.seed_dev ? *g.seed_dev : 0ull) : 0ull;
+    const mdetr_rsrc yr = make_rsrc(g.y, static_cast<unsigned>(((g.T - 1) * g.ldy + g.N) * 4));
+    const mdetr_rsrc rr_ = make_rsrc(has_res ? static_cast<const void *>(g.res) : static_cast<const void *>(g.a),
+                                     has_res ? static_cast<unsigned>(((g.T - 1) * g.ldr + g.N) * 4) : 0u);
+    const mdetr_rsrc mr_ = make_rsrc(MASK ? static_cast<const void *>(g.mask) : static_cast<const void *>(g.a),
+                                     MASK ? static_cast<unsigned>(((g.T - 1) * g.ldm + g.N) * 4) : 0u);
+    float bv[8];
+    int64_t tail_m0 = 0;
+    int tail_n = 0;
+    auto aim_tail = [&](int v) __attribute__((always_inline)) {
+        int col;
+        tile_of(v, col, tail_m0);
+        tail_n = col * BN + pc * 8;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) bv[i] = 0.f;
+        if (g.bias && tail_n < g.N) {                            // N % 8 == 0
+#pragma unroll
+            for (int i = 0; i < 8; ++i) bv[i] = g.bias[tail_n + i];
+        }
+    };
+    auto park = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int a_ = 0; a_ < TN; ++a_)
+#pragma unroll
+            for (int b_ = 0; b_ < TM; ++b_) {
+                float *cr = Cs + (wm * (BM / 2) + b_ * 32 + l31) * (BN + kCPad) + wn * (BN / 2) + a_ * 32 + 4 * half;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    f32x4 o;
+                    o.x = acc[a_][b_][4 * q]; o.y = acc[a_][b_][4 * q + 1]; o.z = acc[a_][b_][4 * q + 2]; o.w = acc[a_][b_][4 * q + 3];
+                    *reinterpret_cast<f32x4 *>(cr + 8 * q) = o;
+                }
+            }
+    };
+    auto drain = [&]() __attribute__((always_inline)) {         // (behind the barrier that follows park)
+        const bool ncol = tail_n < g.N;
+#pragma unroll
+        for (int j0 = 0; j0 < NP; j0 += NPB) {
+            bf16x8 rq[NPB][2], mq[MASK ? NPB : 1][2];
+            unsigned yoff[NPB];                                  // byte offsets of the pieces (kRsrcOob: not stored)
+            f32x4 cq[NPB][2];
+#pragma unroll
+            for (int u = 0; u < NPB; ++u) {
+                const int64_t t = tail_m0 + (tid + kThreadsT * (j0 + u)) / PR;
+                const bool in = ncol && t < g.T;
+                yoff[u] = in ? static_cast<unsigned>((t * g.ldy + tail_n) * 4) : kRsrcOob;
+                const unsigned ro = (has_res && in) ? static_cast<unsigned>((t * g.ldr + tail_n) * 4) : kRsrcOob;
+                rq[u][0] = rsrc_load_bf16x8(rr_, ro, 0u);
+                rq[u][1] = rsrc_load_bf16x8(rr_, ro, 16u);
+                if (MASK) {
+                    const unsigned mo = in ? static_cast<unsigned>((t * g.ldm + tail_n) * 4) : kRsrcOob;
+                    mq[MASK ? u : 0][0] = rsrc_load_bf16x8(mr_, mo, 0u);
+                    mq[MASK ? u : 0][1] = rsrc_load_bf16x8(mr_, mo, 16u);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < NPB; ++u) {
+                const float *cr = Cs + ((tid + kThreadsT * (j0 + u)) / PR) * (BN + kCPad) + pc * 8;
+                cq[u][0] = *reinterpret_cast<const f32x4 *>(cr);
+                cq[u][1] = *reinterpret_cast<const f32x4 *>(cr + 4);
+            }
+#pragma unroll
+            for (int u = 0; u < NPB; ++u) {
+                float o[8] = {cq[u][0].x, cq[u][0].y, cq[u][0].z, cq[u][0].w, cq[u][1].x, cq[u][1].y, cq[u][1].z, cq[u][1].w};
+                float r[8], mk[8];
+                __builtin_memcpy(r, &rq[u][0], 16);
+                __builtin_memcpy(r + 4, &rq[u][1], 16);
+                if (MASK) {
+                    __builtin_memcpy(mk, &mq[MASK ? u : 0][0], 16);
+                    __builtin_memcpy(mk + 4, &mq[MASK ? u : 0][1], 16);
+                }
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    float f = o[i] + bv[i] + r[i];               // (no residual: the load gave zeros)
+                    if (MASK) f = mk[i] <= 0.f ? 0.f : f;        // (threshold_backward's test: a NaN in the mask lets the gradient pass)
+                    f = f < lo ? lo : f;                         // ReLU (NaN passes through, as clamp_min does)
+                    if (g.thresh) {
+                        const uint64_t t = static_cast<uint64_t>(tail_m0 + (tid + kThreadsT * (j0 + u)) / PR);
+                        f = ln_hash(sd, t * static_cast<uint64_t>(g.N) + static_cast<uint64_t>(tail_n + i)) >= g.thresh ? f * g.keep_scale : 0.f;
+                    }
+                    o[i] = f;
+                }
+                f32x4 o0, o1;
+                o0.x = o[0]; o0.y = o[1]; o0.z = o[2]; o0.w = o[3]; o1.x = o[4]; o1.y = o[5]; o1.z = o[6]; o1.w = o[7];
+                rsrc_store_f32x4(yr, o0, yoff[u], 0u);
+                rsrc_store_f32x4(yr, o1, yoff[u], 16u);
+            }
+        }
+    };
+
+    // ---- the slab sequence, exactly tgemm_kernel's: compute cursor (cv, ck), fetch cursor (fv, fk) up to 1 + PF slabs ahead
+    int cv = next_tile(static_cast<int>(blockIdx.x));
+    if (cv >= vtiles) return;
+    int ck = 0, fv = cv, fk = 0;
+    auto advance = [&]() __attribute__((always_inline)) {
+        if (++fk == KT) {
+            fk = 0;
+            fv = next_tile(fv + G);
+            if (fv < vtiles) aim(fv);
+        }
+    };
+    aim(fv);
+    fetch(0, xr[PF - 1], wr[PF - 1]);
+    advance();
+#pragma unroll
+    for (int p = 0; p < PF - 1; ++p)
+        if (fv < vtiles) { fetch(fk, xr[p], wr[p]); advance(); }
+    deposit(0, xr[PF - 1], wr[PF - 1]);
+    if (fv < vtiles) { fetch(fk, xr[PF - 1], wr[PF - 1]); advance(); }
+    clear();
+    __syncthreads();
+    for (int s = 0;; s += PF) {
+#pragma unroll
+        for (int p = 0; p < PF; ++p) {
+            const bool last = ck == KT - 1;
+            if (!last) {
+                deposit((s + p + 1) & 1, xr[p], wr[p]);
+                if (fv < vtiles) { fetch(fk, xr[p], wr[p]); advance(); }
+            }
+            products((s + p) & 1);
+            __syncthreads();
+            ++ck;
+            if (last) {
+                aim_tail(cv);
+                park();
+                __syncthreads();
+                drain();
+                cv = next_tile(cv + G);
+                if (cv >= vtiles) return;
+                __syncthreads();
+                deposit((s + p + 1) & 1, xr[p], wr[p]);
+                if (fv < vtiles) { fetch(fk, xr[p], wr[p]); advance(); }
+                clear();
+                ck = 0;
+                __syncthreads();
+            }
+        }
+    }
+}
+
+template <int BM, int BN, int BK, bool NN, int PF, bool MASK>
+hipError_t launch_tile32(Tgemm32Args g, hipStream_t st)
+{
+    constexpr size_t lds = tgemm32_lds<BM, BN, BK>();
+    static_assert(lds <= 80 * 1024, "two workgroups per CU");
+    auto kern = tgemm32_kernel<BM, BN, BK, NN, PF, MASK>;
+    static bool attr_set[64] = {};
+    int dev_ = 0;
+    if (hipGetDevice(&dev_) != hipSuccess) dev_ = -1;
+    if (dev_ < 0 || dev_ >= 64 || !attr_set[dev_]) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+        if (dev_ >= 0 && dev_ < 64) attr_set[dev_] = true;
+    }
+    const int64_t tiles_m = (g.T + BM - 1) / BM;
+    g.tiles_m = static_cast<int>(tiles_m);
+    g.ny = (g.N + BN - 1) / BN;
+    g.gx = static_cast<int>((tiles_m + 7) / 8 * 8);
+    const int64_t vtiles = static_cast<int64_t>(g.gx) * g.ny;
+    int64_t grid = static_cast<int64_t>(256) * 2;                // persistent: two workgroups per CU (registers and LDS)
+    { const int f = tune_int("tgemm_grid", 0); if (f >= 8 && f % 8 == 0) grid = f; }
+    if (grid > vtiles) grid = vtiles;
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kThreadsT), lds, st, g);
+    return hipGetLastError();
+}
+
+template <bool NN, int PF, bool MASK>
+hipError_t launch_any32(const Tgemm32Args &g, int bm, int bn, hipStream_t st)
+{
+    if (bm == 128 && bn == 128) return launch_tile32<128, 128, 16, NN, 1, MASK>(g, st);          // (one register set: the big tile's registers)
+    if (bm == 128) return launch_tile32<128, 64, 16, NN, PF, MASK>(g, st);
+    return launch_tile32<64, 64, 32, NN, PF, MASK>(g, st);
+}
+
+bool tgemm32_supported(const TgemmProblem &p)
+{
+    const auto al = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    const bool nn = (p.flags & kTgemmNN) != 0;
+    return p.T > 0 && p.T < (1ll << 31) - 256 && p.N > 0 && p.N % 8 == 0 && p.K > 0 && p.K % 8 == 0 && p.a && p.w && p.y && al(p.a) && al(p.w) &&
+           al(p.y) && p.lda % 4 == 0 && p.lda >= p.K && p.ldw % 4 == 0 && p.ldw >= (nn ? p.N : p.K) && p.ldy % 4 == 0 && p.ldy >= p.N &&
+           (!p.res || (al(p.res) && p.ldr % 4 == 0 && p.ldr >= p.N)) && (!p.bias || al(p.bias)) && p.dropout_p >= 0.f && p.dropout_p < 1.f &&
+           !(p.flags & ~(kTgemmRelu | kTgemmNN)) &&
+           // the masked tail: input gradients only (NN), no bias / ReLU / dropout of its own
+           (!p.mask || (nn && al(p.mask) && p.ldm % 4 == 0 && p.ldm >= p.N && p.T * p.ldm < (1ll << 29) && !p.bias && p.dropout_p == 0.f &&
+                        !(p.flags & kTgemmRelu))) &&
+           // buffer-resource addressing: every tensor below 2^31 bytes
+           p.T * p.lda < (1ll << 29) && p.T * p.ldy < (1ll << 29) && p.T * p.ldr < (1ll << 29) && static_cast<int64_t>(nn ? p.K : p.N) * p.ldw < (1ll << 29);
+}
+
+hipError_t tgemm32_launch(const TgemmProblem &p, hipStream_t st)
+{
+    Tgemm32Args g;
+    g.a = static_cast<const float *>(p.a); g.w = static_cast<const float *>(p.w); g.res = static_cast<const float *>(p.res);
+    g.mask = static_cast<const float *>(p.mask); g.bias = static_cast<const float *>(p.bias); g.y = static_cast<float *>(p.y);
+    g.T = p.T; g.lda = p.lda; g.ldw = p.ldw; g.ldr = p.ldr; g.ldy = p.ldy; g.ldm = p.ldm;
+    g.N = p.N; g.K = p.K; g.gx = g.ny = g.tiles_m = 0; g.flags = p.flags;
+    g.thresh = p.dropout_p > 0.f ? ln_threshold(p.dropout_p) : 0u;
+    g.keep_scale = p.dropout_p > 0.f ? 1.f / (1.f - p.dropout_p) : 1.f;
+    g.seed = p.seed; g.seed_dev = p.seed_dev;
+    // Tile choice (profiles/r07a_gemmbench_fp32.json: every product of the step x every tile): the largest tile that still gives the
+    // chip ~1.5 workgroups per CU -- with six MFMA terms per product the LDS-read-to-MFMA ratio decides (encoder 256 -> 256 at
+    // 81 600 rows: 81.0 / 94.3 / 102.5 us on 128 x 128 / 128 x 64 / 64 x 64; 15 360 x 1024 -> 256, 240 big tiles: 67.6 / 61.1 / 69.1)
+    const auto wgs = [&](int m, int n) { return ((p.T + m - 1) / m) * ((p.N + n - 1) / n); };
+    int bm = 64, bn = 64;
+    if (p.N > 64 && wgs(128, 128) >= 400) { bm = 128; bn = 128; }
+    else if (wgs(128, 64) >= 400) { bm = 128; bn = 64; }
+    char tune_buf[16];
+    if (const char *ev = tune_str("tgemm_f32_tile", tune_buf, sizeof(tune_buf))) {       // tests: "128x64"
+        int m = 0, n = 0;
+        if (sscanf(ev, "%dx%d", &m, &n) == 2 && ((m == 64 && n == 64) || (m == 128 && (n == 64 || n == 128)))) { bm = m; bn = n; }
+    }
+    int pf = 2;
+    if (const int f = tune_int("tgemm_f32_pf", 0)) pf = f == 1 ? 1 : 2;                   // tests: register sets in flight (the 128 x 128 tile has one)
+    ProfileScope prof(10, conv_mflop(p.T, static_cast<int64_t>(p.N) * p.K), st, 2.0 * p.T * p.N * p.K / 1e6,
+                      (4.0 * p.T * p.K + 4.0 * p.T * p.N + (p.res ? 4.0 * p.T * p.N : 0.0) + (p.mask ? 4.0 * p.T * p.N : 0.0) + 4.0 * p.N * p.K) / 1e3);
+    if (p.flags & kTgemmNN) {
+        if (p.mask) return pf == 1 ? launch_any32<true, 1, true>(g, bm, bn, st) : launch_any32<true, 2, true>(g, bm, bn, st);
+        return pf == 1 ? launch_any32<true, 1, false>(g, bm, bn, st) : launch_any32<true, 2, false>(g, bm, bn, st);
+    }
+    return pf == 1 ? launch_any32<false, 1, false>(g, bm, bn, st) : launch_any32<false, 2, false>(g, bm, bn, st);
+}
+
 }  // namespace
 
 bool tgemm_supported(const TgemmProblem &p)
 {
+    if (p.f32) return tgemm32_supported(p);
     const auto al = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     const bool nn = (p.flags & kTgemmNN) != 0;
     return p.T > 0 && p.T < (1ll << 31) - 256 && p.N > 0 && p.N % 8 == 0 && p.K > 0 && p.K % 8 == 0 && p.a && p.w && p.y && al(p.a) && al(p.w) &&
@@ -495,6 +930,7 @@ bool tgemm_supported(const TgemmProblem &p)
 
 hipError_t tgemm_launch(const TgemmProblem &p, hipStream_t st)
 {
+    if (p.f32) return tgemm32_launch(p, st);
     TgemmArgs g;
     g.a = static_cast<const __bf16 *>(p.a); g.w = static_cast<const __bf16 *>(p.w); g.res = static_cast<const __bf16 *>(p.res);
     g.mask = static_cast<const __bf16 *>(p.mask); g.ldm = p.ldm;

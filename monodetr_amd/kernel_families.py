@@ -13,7 +13,7 @@ import os
 AUTOTUNE_SWITCHES = ("MDETR_FUSED_LOSSES", "MDETR_FUSED_ADAMW", "MDETR_MSDA_PROLOGUE", "MDETR_FUSED_LN", "MDETR_MSDA_BF16",
                      "MDETR_FUSED_EPILOGUE", "MDETR_GEMM_RELU", "MDETR_CONV3X3", "MDETR_GROUP_NORM", "MDETR_SMALL_WGRAD",
                      "MDETR_CONV_STRIDED", "MDETR_CONV_WGRAD", "MDETR_CONV_STEM", "MDETR_TGEMM", "MDETR_WFOLD", "MDETR_RELU_PREMASK",
-                     "MDETR_HEADS", "MDETR_CHUNK_SUMS", "MDETR_HEAD_TAIL")
+                     "MDETR_HEADS", "MDETR_CHUNK_SUMS", "MDETR_HEAD_TAIL", "MDETR_TGEMM_F32")
 ALL_SWITCHES = AUTOTUNE_SWITCHES
 # The measured configuration.  family -> the GPU tests that hold it to the default path / the framework operators
 # (all in tests/test_fused_gpu.py unless a file is named); a family without green tests is not listed.
@@ -32,6 +32,7 @@ SWITCH_TESTS = {
     "MDETR_CONV_STEM": "test_conv_stem_kernel_matches_the_library_convolution, test_training_step_with_the_convolution_kernels_*",
     "MDETR_TGEMM": "test_tgemm_gpu.py::test_tgemm_*, test_training_step_with_the_token_gemm_kernel_*, test_bottleneck_with_fused_tails_*",
     "MDETR_WFOLD": "test_fold_kernel_*, test_training_step_with_the_fold_kernel_*",
+    "MDETR_TGEMM_F32": "test_tgemm_f32_gpu.py::test_tgemm_f32_*, test_tgemm_f32_gpu.py::test_fp32_modules_with_the_switch_*",
     "MDETR_RELU_PREMASK": "test_tgemm_gpu.py::test_masked_input_gradient_*, test_tgemm_gpu.py::test_bottleneck_stage_with_premasked_relu_*",
     "MDETR_HEADS": "test_sgemm_gpu.py::test_sgemm_*, test_sgemm_gpu.py::test_heads_level_*, test_training_step_with_the_grouped_heads_*",
     "MDETR_HEAD_TAIL": "test_sgemm_gpu.py::test_head_tail_*, test_sgemm_gpu.py::test_training_step_with_the_head_tail_*",
@@ -53,6 +54,8 @@ COMMITTED_SWITCHES = {
     # MDETR_RELU_PREMASK (round 5): the ReLU backward masks inside the bottlenecks (conv2 -> conv3) and between consecutive blocks of a
     # stage applied in the consumers' input-gradient products (mdetr_tgemm_masked), 23 elementwise passes less: 436.2 -> 441.4 img/s in
     # one call, bit-identical gradients (profiles/r05z2_step_ab_premask.log).
+    # MDETR_TGEMM_F32: the fp32 form of the same products (mdetr_tgemm_f32: three-way bf16 split, six MFMA terms).  Opt-in: on NO
+    # committed list; whether it joins "fp32" is decided on the step A/B recorded in DESIGN.md 3.3.
     "bf16": ("MDETR_FUSED_LOSSES", "MDETR_FUSED_ADAMW", "MDETR_FUSED_LN", "MDETR_MSDA_PROLOGUE", "MDETR_MSDA_BF16",
              "MDETR_FUSED_EPILOGUE", "MDETR_GEMM_RELU", "MDETR_CONV3X3", "MDETR_GROUP_NORM", "MDETR_SMALL_WGRAD",
              "MDETR_CONV_WGRAD", "MDETR_CONV_STRIDED", "MDETR_CONV_STEM", "MDETR_TGEMM", "MDETR_WFOLD", "MDETR_RELU_PREMASK", "MDETR_HEADS",
@@ -89,6 +92,7 @@ def apply_switches(names):
     ms_deform_attn._FUSED_PROLOGUE = "MDETR_MSDA_PROLOGUE" in names
     add_ln_ext.ENABLED = "MDETR_FUSED_LN" in names
     linear._TGEMM = "MDETR_TGEMM" in names
+    linear._TGEMM_F32 = "MDETR_TGEMM_F32" in names
     heads.ENABLED = "MDETR_HEADS" in names
     wfold_ext.ENABLED = "MDETR_WFOLD" in names
     linear._PREMASK = "MDETR_RELU_PREMASK" in names

@@ -3,7 +3,9 @@ channels-last maps) with its autograd structure, and the router that decides whi
 
 bf16 operands on the GPU with MDETR_TGEMM (the committed bf16 list): forward and input gradient through csrc/tgemm.hip -- bias,
 ReLU, Dropout, "+ identity" and the residual-path gradient in the product's epilogue -- and the weight + bias gradient through
-csrc/twgrad.hip (>= 1 024 rows) or csrc/small_wgrad.hip, chunk partials summed by csrc/colsum.hip.  Everything else (fp32, autocast,
+csrc/twgrad.hip (>= 1 024 rows) or csrc/small_wgrad.hip, chunk partials summed by csrc/colsum.hip.  fp32 operands with
+MDETR_TGEMM_F32 (opt-in): forward and input gradient through the fp32 form of csrc/tgemm.hip, same epilogues; their weight gradients
+keep the library route.  Everything else (fp32 without that switch, autocast,
 CPU tensors, operands the kernels' alignment rules refuse) takes the library GEMMs with the SAME autograd functions: a batched
 split-K product for tall weight gradients (the library's single NT GEMM runs 16 workgroups deep at [81 600, 256]^T x [81 600, 256]:
 205 us against 35), `colsum` for the bias.  Rules, not probing: nothing is timed at run time.
@@ -23,6 +25,9 @@ _GEMM_RELU = os.environ.get("MDETR_GEMM_RELU") == "1"
 # MDETR_TGEMM=1: forward and input-gradient products of bf16 layers through csrc/tgemm.hip, their elementwise tails (bias, ReLU,
 # Dropout, "+ identity", the residual-path gradient's accumulation) inside its epilogue.  kernel_families decides (committed for bf16).
 _TGEMM = os.environ.get("MDETR_TGEMM") == "1"
+# MDETR_TGEMM_F32=1: the same products of fp32 layers through the fp32 form of csrc/tgemm.hip (mdetr_tgemm_f32: each operand split into
+# three bf16 parts, six matrix-instruction terms per product -- fp32-accurate).  Opt-in: on no committed list.
+_TGEMM_F32 = os.environ.get("MDETR_TGEMM_F32") == "1"
 
 
 # rows from which a bf16 weight gradient takes csrc/twgrad.hip instead of csrc/small_wgrad.hip: the decoder's 4 400 and layer4's 3 840
@@ -60,8 +65,21 @@ def relu_token_of(t):
     return getattr(t, "_mdetr_relu_token", None) if _PREMASK else None
 
 
+def _kernel_dtype(dtype):
+    """Is `dtype` one csrc/tgemm.hip takes under the switch that is on?  (bf16: MDETR_TGEMM; fp32: MDETR_TGEMM_F32)"""
+    return (_TGEMM and dtype == torch.bfloat16) or (_TGEMM_F32 and dtype == torch.float32)
+
+
+# fp32 input gradients (the NN form) below this many rows stay with the library: the decoder's 4 400-row products measured 13.7 vs
+# 12.2 us (256 -> 256) and 41.6 vs 35.8 us (1032 -> 256) against a library spread of 0.2 / 1.1 us, while the forward forms at 4 400
+# rows and every form from 15 360 rows on are faster than or level with the library route (profiles/r07a_gemmbench_fp32.json)
+_F32_NN_MIN_TOKENS = 8192
+
+
 def _tgemm_ok(x2, weight, bias=None, res2=None, nn=False):
-    if not _TGEMM:
+    if not _kernel_dtype(x2.dtype):
+        return False
+    if nn and x2.dtype == torch.float32 and x2.shape[0] < _F32_NN_MIN_TOKENS:
         return False
     from .. import tgemm_ext
     return tgemm_ext.supported(x2, weight, nn=nn, res=res2, bias=bias)
@@ -146,8 +164,9 @@ def _weight_bias_grads(x2, dy2, weight, need_w, need_b, bias_dtype=None, out_dty
     return dw, db
 
 
-def _fwd_product(x2, weight, bias, relu=False, res2=None, dropout_p=0.0, seed=0, seed_dev=None, out_dtype=torch.bfloat16):
-    """x2 W^T + bias (+ res2, ReLU, Dropout) through csrc/tgemm.hip (the caller has asked `_tgemm_ok`)."""
+def _fwd_product(x2, weight, bias, relu=False, res2=None, dropout_p=0.0, seed=0, seed_dev=None, out_dtype=None):
+    """x2 W^T + bias (+ res2, ReLU, Dropout) through csrc/tgemm.hip (the caller has asked `_tgemm_ok`); out_dtype: the operands'
+    unless given (fp32 from bf16 operands: `wide_out`)."""
     from .. import tgemm_ext
     return tgemm_ext.tgemm(x2, weight, bias, res2, relu=relu, out_dtype=out_dtype, dropout_p=dropout_p, seed=seed, seed_dev=seed_dev)
 
@@ -194,7 +213,7 @@ class _TokenLinearSkip(torch.autograd.Function):
         if _tgemm_ok(q2, weight, bias):
             seed, seed_dev = _drop_seed(q, dropout_p)
             y = _fwd_product(q2, weight, bias, relu, None, dropout_p, seed, seed_dev,
-                             torch.float32 if wide_out else torch.bfloat16).view(q.shape[:-1] + (weight.shape[0],))
+                             torch.float32 if wide_out else q2.dtype).view(q.shape[:-1] + (weight.shape[0],))
         elif dropout_p > 0.0 or wide_out:
             raise RuntimeError("token_linear_skip: dropout and the fp32 result exist in csrc/tgemm.hip's epilogue only")
         elif relu:                                                   # library GEMM with the RELU_BIAS epilogue (as _TokenLinear)
@@ -233,7 +252,9 @@ def token_linear_skip(x, weight, bias=None, pos=None, relu=False, dropout_p=0.0,
             and (not relu or skip_relu_fusable(bias, x, weight)) and (dropout_p <= 0.0 or skip_dropout_fusable(x, weight, bias)) \
             and (not wide_out or (not relu and x.is_cuda and x.dtype == torch.bfloat16 and _tgemm_ok(x.reshape(-1, x.shape[-1]), weight, bias))):
         # relu_token: x is a ReLU output with this call as its only consumer (`ReluToken`): the mask goes into the input gradient here
-        premask = relu_token is not None and pos is None and x.dtype == torch.bfloat16 and _tgemm_ok(x.reshape(-1, x.shape[-1]), weight, bias)
+        # (fp32: only where the fp32 masked form takes the operands -- `_kernel_dtype` + `_tgemm_ok`; otherwise the producer masks itself)
+        premask = relu_token is not None and pos is None and _kernel_dtype(x.dtype) and _tgemm_ok(x.reshape(-1, x.shape[-1]), weight, bias) \
+            and (x.dtype != torch.float32 or x.numel() // x.shape[-1] >= _F32_NN_MIN_TOKENS)
         if premask:
             relu_token.premasked = True
         return _TokenLinearSkip.apply(x, weight, bias, pos, relu, dropout_p, premask, wide_out, out_token if relu else None)
@@ -269,7 +290,7 @@ class _TokenLinear(torch.autograd.Function):
         x2 = x.reshape(-1, x.shape[-1])
         if _tgemm_ok(x2, weight, bias):
             seed, seed_dev = _drop_seed(x, dropout_p)
-            y = _fwd_product(x2, weight, bias, fused_relu, None, dropout_p, seed, seed_dev, torch.float32 if wide_out else torch.bfloat16)
+            y = _fwd_product(x2, weight, bias, fused_relu, None, dropout_p, seed, seed_dev, torch.float32 if wide_out else x2.dtype)
             y = y.view(x.shape[:-1] + (weight.shape[0],))
             ctx.fused_relu = bool(fused_relu)
             if fused_relu:
@@ -442,10 +463,10 @@ def pointwise_conv_skip(x, weight, bias=None, relu=False, relu_token=None, hand_
 
 
 def pointwise_residual_relu_eligible(x, weight, bias, identity):
-    """Can `pointwise_conv_residual_relu` take relu(conv1x1(x) + identity)?  channels-last bf16 activations whose token views are
-    views, a bf16 weight, csrc/tgemm.hip's shape rules."""
-    if not (_TGEMM and x.dim() == 4 and identity.dim() == 4 and x.dtype == torch.bfloat16 and identity.dtype == torch.bfloat16
-            and weight.dtype == torch.bfloat16 and not torch.is_autocast_enabled()
+    """Can `pointwise_conv_residual_relu` take relu(conv1x1(x) + identity)?  channels-last activations whose token views are
+    views, activations and weight of ONE dtype that csrc/tgemm.hip takes under the switch that is on, its shape rules."""
+    if not (x.dim() == 4 and identity.dim() == 4 and _kernel_dtype(x.dtype) and identity.dtype == x.dtype
+            and weight.dtype == x.dtype and not torch.is_autocast_enabled()
             and x.is_contiguous(memory_format=torch.channels_last) and identity.is_contiguous(memory_format=torch.channels_last)):
         return False
     B, C, H, W = x.shape
@@ -481,7 +502,7 @@ def pointwise_conv_residual_relu(x, weight, bias, identity, in_token=None, hand_
 def pointwise_relu_fusable(x, weight, bias):
     """Would `pointwise_conv(..., relu=True)` run the ReLU inside the GEMM?  (callers that apply an in-place ReLU
     themselves otherwise)"""
-    if not (_GEMM_RELU or _TGEMM):                    # the default path pays nothing for the question
+    if not (_GEMM_RELU or _TGEMM or _TGEMM_F32):      # the default path pays nothing for the question
         return False
     C = x.shape[1]
     return (x.numel() // C >= _MIN_TOKENS and torch.is_grad_enabled() and not torch.is_autocast_enabled()

@@ -7,6 +7,10 @@ buffer sets to exceed the 256 MB Infinity Cache (a product never finds its own p
 algorithmic bytes / time against 8 TB/s and flops / time against 2.5 PFLOP/s, the larger of the two floors as `bound_us`.
 
     python -m monodetr_amd.tools.gemmbench [--sweep] [--only enc,l3] [--reps 20] [--out gpurun_out/gemmbench.json]
+
+--dtype fp32: the same shape list with fp32 operands -- the library's fp32 GEMM plus the tail passes the fp32 call sites run today
+against csrc/tgemm.hip's fp32 form (mdetr_tgemm_f32); every figure is the median of --repeats (default 3) graph timings, and the
+library's min / max over those repeats is recorded beside it (`library_spread_us`).
 """
 import argparse
 import json
@@ -85,7 +89,19 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--tune", default="", help="extra tgemm variants as MDETR_TUNE strings, e.g. 'tgemm_tile=128x64,tgemm_pf=1;tgemm_grid=512'")
     ap.add_argument("--eager", action="store_true", help="plain launches instead of graph replays (counter passes)")
+    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp32"), help="operand type: bf16 (mdetr_tgemm) or fp32 (mdetr_tgemm_f32)")
+    ap.add_argument("--repeats", type=int, default=0, help="graph timings per figure, the median is reported (default: 1 for bf16, 3 for fp32)")
     a = ap.parse_args()
+    f32 = a.dtype == "fp32"
+    dt, es = (torch.float32, 4) if f32 else (torch.bfloat16, 2)
+    repeats = a.repeats or (3 if f32 else 1)
+    tile_key, pf_key = ("tgemm_f32_tile", "tgemm_f32_pf") if f32 else ("tgemm_tile", "tgemm_pf")
+    tiles = (("128x128", ("1",)), ("128x64", ("1", "2")), ("64x64", ("1", "2"))) if f32 else \
+        tuple((t, ("1", "2")) for t in ("128x128", "128x64", "64x128", "64x64"))
+
+    def timed(fn, nsets):
+        ts = sorted(graph_time(fn, nsets, a.reps) for _ in range(repeats))
+        return ts[len(ts) // 2], ts
     global EAGER
     EAGER = a.eager
     from monodetr_amd import bias_act_ext, tgemm_ext
@@ -99,15 +115,15 @@ def main():
     for name, T, K, N, tail, nn in cases:
         if a.only and not any(k in name for k in a.only.split(",")):
             continue
-        byts = 2 * (T * K + T * N * (2 if tail in ("res_relu", "accum") else 1) + N * K)
+        byts = es * (T * K + T * N * (2 if tail in ("res_relu", "accum") else 1) + N * K)
         flops = 2.0 * T * N * K
-        nsets = max(1, min(6, int(300e6 // (2 * T * (K + 2 * N))) + 1))
+        nsets = max(1, min(6, int(300e6 // (es * T * (K + 2 * N))) + 1))
         gen = torch.Generator(device="cpu").manual_seed(T + K + N)
-        xs = [(torch.randn(T, K, generator=gen) * 0.5).to(torch.bfloat16).to(dev) for _ in range(nsets)]
-        w = ((torch.randn(K, N, generator=gen) if nn else torch.randn(N, K, generator=gen)) * 0.05).to(torch.bfloat16).to(dev)
-        b = torch.randn(N, generator=gen).to(torch.bfloat16).to(dev)
-        rs = [torch.randn(T, N, generator=gen).to(torch.bfloat16).to(dev) for _ in range(nsets)] if tail in ("res_relu", "accum") else None
-        ys = [torch.empty(T, N, dtype=torch.bfloat16, device=dev) for _ in range(nsets)]
+        xs = [(torch.randn(T, K, generator=gen) * 0.5).to(dt).to(dev) for _ in range(nsets)]
+        w = ((torch.randn(K, N, generator=gen) if nn else torch.randn(N, K, generator=gen)) * 0.05).to(dt).to(dev)
+        b = torch.randn(N, generator=gen).to(dt).to(dev)
+        rs = [torch.randn(T, N, generator=gen).to(dt).to(dev) for _ in range(nsets)] if tail in ("res_relu", "accum") else None
+        ys = [torch.empty(T, N, dtype=dt, device=dev) for _ in range(nsets)]
         row = {"T": T, "K": K, "N": N, "tail": tail, "nn": nn, "bound_us": round(max(byts / HBM, flops / MFMA) * 1e6, 2),
                "hbm_us": round(byts / HBM * 1e6, 2), "mfma_us": round(flops / MFMA * 1e6, 2)}
 
@@ -126,7 +142,9 @@ def main():
             if tail == "relu_drop":
                 return bias_act_ext.bias_act(y, None, None, relu=True, dropout_p=0.1, seed=5)
             return y
-        row["library_us"] = graph_time(lib, nsets, a.reps)
+        row["library_us"], spread = timed(lib, nsets)
+        if repeats > 1:
+            row["library_spread_us"] = [spread[0], spread[-1]]
 
         # ---- tgemm, the tail inside
         def ours(i):
@@ -136,16 +154,16 @@ def main():
             return tgemm_ext.tgemm(x, w, b, rs[i] if tail == "res_relu" else None, relu=tail in ("relu", "res_relu", "relu_drop"),
                                    out=ys[i], dropout_p=0.1 if tail == "relu_drop" else 0.0, seed=5)
         os.environ.pop("MDETR_TUNE", None)
-        row["tgemm_us"] = graph_time(ours, nsets, a.reps)
+        row["tgemm_us"] = timed(ours, nsets)[0]
         if a.sweep:
-            for tile in ("128x128", "128x64", "64x128", "64x64"):
-                for pf in ("1", "2"):
-                    os.environ["MDETR_TUNE"] = "tgemm_tile=%s,tgemm_pf=%s" % (tile, pf)
-                    row["tgemm_%s_pf%s_us" % (tile, pf)] = graph_time(ours, nsets, a.reps)
+            for tile, pfs in tiles:
+                for pf in pfs:
+                    os.environ["MDETR_TUNE"] = "%s=%s,%s=%s" % (tile_key, tile, pf_key, pf)
+                    row["tgemm_%s_pf%s_us" % (tile, pf)] = timed(ours, nsets)[0]
             os.environ.pop("MDETR_TUNE", None)
         for var in [v for v in a.tune.split(";") if v]:               # extra variants: "key=value,key=value;..." (each group timed once)
             os.environ["MDETR_TUNE"] = var
-            row["tgemm[%s]_us" % var] = graph_time(ours, nsets, a.reps)
+            row["tgemm[%s]_us" % var] = timed(ours, nsets)[0]
         os.environ.pop("MDETR_TUNE", None)
         best = min(v for k, v in row.items() if k.startswith("tgemm") and k.endswith("_us"))
         row["tgemm_best_us"], row["tgemm_frac_of_bound"] = best, round(row["bound_us"] / best, 3)
