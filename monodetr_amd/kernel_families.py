@@ -25,19 +25,19 @@ SWITCH_TESTS = {
     "MDETR_MSDA_BF16": "test_msda_bf16_kernels_*, test_msda_function_with_native_bf16_*, test_training_step_with_bf16_msda_*, test_msda_gpu.py::test_bf16_native_full_encoder_shape_vs_oracle",
     "MDETR_FUSED_EPILOGUE": "test_bias_act_kernel_*, test_training_step_with_fused_tails_*",
     "MDETR_GEMM_RELU": "test_library_gemm_relu_epilogue_*, test_training_step_with_fused_tails_*",
-    "MDETR_SMALL_WGRAD": "test_small_wgrad_kernel_*, test_training_step_with_the_small_wgrad_kernel_*",
+    "MDETR_SMALL_WGRAD": "test_small_wgrad_kernel_*, test_training_step_with_the_small_wgrad_kernel_*, test_exact_products_gpu.py::test_exact_small_wgrad",
     "MDETR_GROUP_NORM": "test_group_norm_kernel_*, test_training_step_with_the_group_norm_kernel_*",
-    "MDETR_CONV_STRIDED": "test_conv_strided_kernel_matches_the_library_convolution, test_training_step_with_the_convolution_kernels_*",
-    "MDETR_CONV_WGRAD": "test_conv_wgrad_kernel_matches_the_library_weight_gradient, test_conv_strided_kernel_*, test_training_step_with_the_convolution_kernels_*",
-    "MDETR_CONV_STEM": "test_conv_stem_kernel_matches_the_library_convolution, test_training_step_with_the_convolution_kernels_*",
-    "MDETR_TGEMM": "test_tgemm_gpu.py::test_tgemm_*, test_training_step_with_the_token_gemm_kernel_*, test_bottleneck_with_fused_tails_*",
+    "MDETR_CONV_STRIDED": "test_conv_strided_kernel_matches_the_library_convolution, test_training_step_with_the_convolution_kernels_*, test_exact_products_gpu.py::test_exact_conv_strided_*",
+    "MDETR_CONV_WGRAD": "test_conv_wgrad_kernel_matches_the_library_weight_gradient, test_conv_strided_kernel_*, test_training_step_with_the_convolution_kernels_*, test_exact_products_gpu.py::test_exact_conv_wgrad_*, test_exact_products_gpu.py::test_exact_token_weight_gradient",
+    "MDETR_CONV_STEM": "test_conv_stem_kernel_matches_the_library_convolution, test_training_step_with_the_convolution_kernels_*, test_exact_products_gpu.py::test_exact_conv_stem",
+    "MDETR_TGEMM": "test_tgemm_gpu.py::test_tgemm_*, test_training_step_with_the_token_gemm_kernel_*, test_bottleneck_with_fused_tails_*, test_exact_products_gpu.py::test_exact_tgemm_bf16_*, test_exact_products_gpu.py::test_exact_decimate_and_pointwise_conv",
     "MDETR_WFOLD": "test_fold_kernel_*, test_training_step_with_the_fold_kernel_*",
-    "MDETR_TGEMM_F32": "test_tgemm_f32_gpu.py::test_tgemm_f32_*, test_tgemm_f32_gpu.py::test_fp32_modules_with_the_switch_*",
-    "MDETR_RELU_PREMASK": "test_tgemm_gpu.py::test_masked_input_gradient_*, test_tgemm_gpu.py::test_bottleneck_stage_with_premasked_relu_*",
-    "MDETR_HEADS": "test_sgemm_gpu.py::test_sgemm_*, test_sgemm_gpu.py::test_heads_level_*, test_training_step_with_the_grouped_heads_*",
+    "MDETR_TGEMM_F32": "test_tgemm_f32_gpu.py::test_tgemm_f32_*, test_tgemm_f32_gpu.py::test_fp32_modules_with_the_switch_*, test_exact_products_gpu.py::test_exact_tgemm_f32_*",
+    "MDETR_RELU_PREMASK": "test_tgemm_gpu.py::test_masked_input_gradient_*, test_tgemm_gpu.py::test_bottleneck_stage_with_premasked_relu_*, test_exact_products_gpu.py::test_exact_tgemm_masked_*",
+    "MDETR_HEADS": "test_sgemm_gpu.py::test_sgemm_*, test_sgemm_gpu.py::test_heads_level_*, test_training_step_with_the_grouped_heads_*, test_exact_products_gpu.py::test_exact_sgemm_grouped_*",
     "MDETR_HEAD_TAIL": "test_sgemm_gpu.py::test_head_tail_*, test_sgemm_gpu.py::test_training_step_with_the_head_tail_*",
     "MDETR_CHUNK_SUMS": "test_colsum_gpu.py::test_chunk_sums_*, test_colsum_gpu.py::test_deferred_chunk_sums_*",
-    "MDETR_CONV3X3": "test_conv3x3_kernel_matches_the_library_convolution, test_training_step_with_the_conv3x3_kernel_*, test_conv3x3_module_with_a_trainable_bias_*",
+    "MDETR_CONV3X3": "test_conv3x3_kernel_matches_the_library_convolution, test_training_step_with_the_conv3x3_kernel_*, test_conv3x3_module_with_a_trainable_bias_*, test_exact_products_gpu.py::test_exact_conv3x3_*",
 }
 COMMITTED_SWITCHES = {
     # (MDETR_CONV3X3: 1.6-3.5x MIOpen per kernel on the four ResNet stages, profiles/r02a_fusedbench.json; the step 249.3 vs

@@ -802,6 +802,11 @@ def test_conv_stem_kernel_matches_the_library_convolution(B, H, W):
     ref = torch.relu(torch.nn.functional.conv2d(x.float(), w.float(), shift, stride=2, padding=3))
     assert y.shape == ref.shape
     assert (y.float() - ref).abs().max().item() <= 1.2e-2 * max(1.0, ref.abs().max().item())
+    # element by element against fp64 on the same bf16 operands: one bf16 rounding of an fp32-accumulated sum of 147 exact products
+    from gemm_bounds import assert_product_close, conv2d_f64
+    ref64 = torch.relu(conv2d_f64(x.double(), w.double(), shift.double(), stride=2, padding=3))
+    mag64 = conv2d_f64(x.double().abs(), w.double().abs(), shift.double().abs(), stride=2, padding=3)
+    assert_product_close(y, ref64, mag64, 147, "stem B=%d H=%d W=%d" % (B, H, W))
 
 
 def _library_convolutions(step):
@@ -919,6 +924,9 @@ def test_small_wgrad_kernel_matches_the_library_products(T, N, K, dtype):
     rw, rb = dy.double().t() @ x.double(), dy.double().sum(0)
     tol = 2 ** -8 if dtype == torch.bfloat16 else 1e-5
     assert (dw.double() - rw).abs().max() <= tol * rw.abs().max() and (db.double() - rb).abs().max() <= tol * max(1.0, rb.abs().max().item())
+    from gemm_bounds import assert_product_close
+    assert_product_close(dw, rw, dy.double().abs().t() @ x.double().abs(), T, "small_wgrad dW")       # element-wise: fp32 sums over T rows, one rounding
+    assert_product_close(db, rb, dy.double().abs().sum(0), T, "small_wgrad db")
     dw2, db2 = small_wgrad_ext.small_wgrad(dy, x, dtype)
     assert torch.equal(dw, dw2) and torch.equal(db, db2)                    # fixed summation order: deterministic
 
@@ -962,8 +970,23 @@ def test_decimate_kernel_and_the_projection_shortcut_as_a_token_gemm(B, C, H, W,
         want = torch.nn.functional.conv2d(x.float(), w.float(), b.float(), stride=2)
         assert (got.float() - want).abs().max() <= 2e-2 * want.abs().max()
         go = torch.randn(got.shape, device="cuda", generator=g).to(dtype)
-        for a, c in zip(torch.autograd.grad(got, [x, w], go), torch.autograd.grad(want, [x, w], go.float())):
+        grads = torch.autograd.grad(got, [x, w], go)
+        for a, c in zip(grads, torch.autograd.grad(want, [x, w], go.float())):
             assert (a.float() - c.float()).abs().max() <= 2e-2 * c.float().abs().max()
+        # element by element against fp64 on the same bf16 operands (one rounding of an fp32-accumulated product each)
+        from gemm_bounds import assert_product_close, conv2d_f64
+        from monodetr_amd import small_wgrad_ext
+        x64, w64 = x.detach().double().requires_grad_(True), w.detach().double().requires_grad_(True)
+        ref = conv2d_f64(x64, w64, b.double(), stride=2)
+        gx, gw = torch.autograd.grad(ref, (x64, w64), go.double())
+        xa, wa = x.detach().double().abs().requires_grad_(True), w.detach().double().abs().requires_grad_(True)
+        mag = conv2d_f64(xa, wa, b.double().abs(), stride=2)
+        mx, mw = torch.autograd.grad(mag, (xa, wa), go.double().abs())
+        T = got.numel() // N
+        assert_product_close(got, ref.detach(), mag.detach(), C, "decimate route y")
+        assert_product_close(grads[0], gx, mx, N, "decimate route dx")
+        if T <= small_wgrad_ext.MAX_ROWS:       # (beyond it the library route rounds each of its split-K chunk products to bf16: not ONE rounding)
+            assert_product_close(grads[1], gw, mw, T, "decimate route dw")
 
 
 @pytest.mark.parametrize("B,C,H,W", [(8, 64, 192, 640), (1, 8, 7, 9), (2, 64, 5, 6)])

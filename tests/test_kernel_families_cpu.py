@@ -39,7 +39,8 @@ def test_apply_switches_sets_and_clears_the_module_flags():
 def test_committed_switch_list_is_the_configuration(monkeypatch):
     """Every committed family names the GPU tests that hold it, those tests exist, and the environment only overrides
     the list when it says so."""
-    src = "".join(open(os.path.join(os.path.dirname(__file__), f)).read() for f in ("test_fused_gpu.py", "test_msda_gpu.py", "test_tgemm_gpu.py", "test_sgemm_gpu.py", "test_colsum_gpu.py"))
+    src = "".join(open(os.path.join(os.path.dirname(__file__), f)).read() for f in ("test_fused_gpu.py", "test_msda_gpu.py", "test_tgemm_gpu.py", "test_sgemm_gpu.py", "test_colsum_gpu.py",
+                                                                                             "test_exact_products_gpu.py"))
     for precision, fams in bench.COMMITTED_SWITCHES.items():
         for fam in fams:
             assert fam in bench.ALL_SWITCHES and fam in bench.SWITCH_TESTS, fam

@@ -209,9 +209,10 @@ def test_switch_is_listed_applied_and_not_committed(monkeypatch):
     assert "MDETR_TGEMM_F32" in kf.ALL_SWITCHES and "MDETR_TGEMM_F32" in kf.SWITCH_TESTS
     assert all("MDETR_TGEMM_F32" not in fams for fams in kf.COMMITTED_SWITCHES.values())
     import os
-    src = open(os.path.join(os.path.dirname(__file__), "test_tgemm_f32_gpu.py")).read()
     for pat in kf.SWITCH_TESTS["MDETR_TGEMM_F32"].split(","):
-        assert "def " + pat.strip().split("::")[-1].rstrip("*") in src, pat
+        name, stem = pat.strip().split("::")                         # every pattern names its file, and a test of that file
+        assert name in ("test_tgemm_f32_gpu.py", "test_exact_products_gpu.py"), pat
+        assert "def " + stem.rstrip("*") in open(os.path.join(os.path.dirname(__file__), name)).read(), pat
     try:
         kf.apply_switches({"MDETR_TGEMM_F32"})
         assert linear._TGEMM_F32 and not linear._TGEMM
