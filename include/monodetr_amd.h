@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MDETR_ABI_VERSION 13
+#define MDETR_ABI_VERSION 14
 
 /* element types of the floating-point tensors */
 #define MDETR_F32 0
@@ -41,6 +41,7 @@ extern "C" {
 #define MDETR_E_ARG        -1   /* bad size / null pointer / unsupported dtype */
 #define MDETR_E_HIP        -2   /* HIP runtime or launch error (message has the hipError string) */
 #define MDETR_E_ALIGN      -3   /* pointer not 16-byte aligned */
+#define MDETR_E_UNSUPPORTED -4  /* this entry has no kernel for the geometry; nothing was written (mdetr_msda_backward_to) */
 
 int mdetr_abi_version(void);
 const char *mdetr_last_error(void);
@@ -228,6 +229,22 @@ int mdetr_msda_backward_bf16(const void *value, const int64_t *spatial_shapes, c
                              int B, int S, int M, int D, int L, int Lq, int P,
                              const int64_t *spatial_shapes_host, const int64_t *level_start_host,
                              void *workspace, int64_t workspace_bytes, int device, void *stream);
+/*
+ * The one-pass backward (ABI 14) with grad_value written in the type its consumer reads: value / grad_out fp32 (dtype MDETR_F32)
+ * or bf16 (MDETR_BF16), grad_value fp32 or bf16 (grad_value_dtype) independently of them, B * S * M * D elements; grad_loc and
+ * grad_attn stay fp32.  Every consumer of grad_value in a bf16 model is a bf16 token GEMM, and an fp32 grad_value costs a cast
+ * launch (read 4, write 2 bytes per element) on top of the wider store.  The bf16 result is the fp32 result rounded once to nearest
+ * even, bit for bit, except in calls that use the side buffer for corners beyond every block's reach (or non-finite gradients):
+ * there the finalize pass adds the side buffer to the already rounded core value and rounds again -- at most one bf16 ulp away.
+ * Only the one-pass kernel writes bf16: returns MDETR_E_UNSUPPORTED -- and has written nothing -- where the geometry does not
+ * qualify for it (D != 32, L * P not a multiple of 4, no workspace, MDETR_TUNE forcing another strategy); the caller then takes
+ * mdetr_msda_backward_ex / _bf16 and converts.  Workspace and host geometry as for mdetr_msda_backward_ex.
+ */
+int mdetr_msda_backward_to(int dtype, int grad_value_dtype, const void *value, const float *loc, const float *attn,
+                           const void *grad_out, void *grad_value, float *grad_loc, float *grad_attn,
+                           int B, int S, int M, int D, int L, int Lq, int P,
+                           const int64_t *spatial_shapes_host, const int64_t *level_start_host,
+                           void *workspace, int64_t workspace_bytes, int device, void *stream);
 
 /*
  * The arithmetic MSDeformAttn.forward performs between its projections and the sampling operator
@@ -570,6 +587,19 @@ typedef struct {
     int32_t chunks, out_dtype;
 } mdetr_chunk_job;
 int mdetr_chunk_sums(const mdetr_chunk_job *jobs, int njobs, int device, void *stream);
+/* The same launch for jobs that read a column range of a wider partial set (ABI 14): row k of job i starts at part_i + k * pitch_i
+ * (pitch >= cols, pitch % 4 == 0; `part` already points at the job's first column and is 16-byte aligned).  Both column sums of a
+ * LayerNorm site (d gamma, d beta: the two halves of mdetr_add_layernorm_backward's partial [nb, 2 * cols]) are two such jobs, each
+ * with a result tensor of its own.  A job of more than 128 chunks is added by 32 row lanes (lane r: chunks r, r + 32, ... in order;
+ * the lanes in lane order); the form follows from the job's chunk count alone, so a sum has the same bits in any launch, and every
+ * job mdetr_chunk_sums could take before ABI 14 with <= 128 chunks keeps its order and bits. */
+typedef struct {
+    const float *part;
+    void *out;
+    int64_t cols, pitch;
+    int32_t chunks, out_dtype;
+} mdetr_chunk_job_pitched;
+int mdetr_chunk_sums_pitched(const mdetr_chunk_job_pitched *jobs, int njobs, int device, void *stream);
 int mdetr_column_sum_to(int dtype, const void *x, void *out, int out_dtype, void *workspace, int64_t workspace_bytes,
                         int64_t rows, int cols, int64_t ld, int device, void *stream);
 

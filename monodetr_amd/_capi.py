@@ -16,7 +16,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MDETR_LIB_PATH") or os.path.join(_HERE, "libmonodetr_amd.so")
 
 MDETR_F32, MDETR_F64, MDETR_BF16 = 0, 1, 2
-ABI_VERSION = 13
+MDETR_E_UNSUPPORTED = -4
+ABI_VERSION = 14
 
 _c_int, _c_vp = ctypes.c_int, ctypes.c_void_p
 
@@ -58,6 +59,7 @@ SIGNATURES = {
     "mdetr_head_tail_forward": (_c_int, [_c_vp] * 10 + [_c_int] * 6 + [_c_int, _c_vp]),
     "mdetr_head_tail_backward": (_c_int, [_c_vp] * 13 + [_c_int] * 6 + [_c_int, _c_vp]),
     "mdetr_chunk_sums": (_c_int, [_c_vp, _c_int, _c_int, _c_vp]),
+    "mdetr_chunk_sums_pitched": (_c_int, [_c_vp, _c_int, _c_int, _c_vp]),
     "mdetr_column_sum_to": (_c_int, [_c_int, _c_vp, _c_vp, _c_int, _c_vp, ctypes.c_int64, ctypes.c_int64, _c_int, ctypes.c_int64, _c_int, _c_vp]),
     "mdetr_add_layernorm_forward": (_c_int, [_c_int, _c_int] + [_c_vp] * 7 + [ctypes.c_int64, _c_int, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, _c_vp, _c_int, _c_vp]),
     "mdetr_add_layernorm_partial_rows": (ctypes.c_int64, [ctypes.c_int64]),
@@ -86,6 +88,7 @@ SIGNATURES = {
     "mdetr_kitti_preprocess": (_c_int, [_c_vp, _c_vp, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_int, _c_vp]),
     "mdetr_msda_forward_bf16": (_c_int, [_c_vp] * 6 + [_c_int] * 7 + [_c_int, _c_vp]),
     "mdetr_msda_backward_bf16": (_c_int, [_c_vp] * 9 + [_c_int] * 7 + [_c_vp, _c_vp, _c_vp, ctypes.c_int64, _c_int, _c_vp]),
+    "mdetr_msda_backward_to": (_c_int, [_c_int, _c_int] + [_c_vp] * 7 + [_c_int] * 7 + [_c_vp, _c_vp, _c_vp, ctypes.c_int64, _c_int, _c_vp]),
     "mdetr_msda_prologue_forward": (_c_int, [_c_int, _c_int] + [_c_vp] * 6 + [_c_int] * 6 + [ctypes.c_int64] * 3 + [_c_int, _c_vp]),
     "mdetr_gather_flat": (_c_int, [_c_vp, _c_int] + [_c_vp] * 6 + [_c_int, _c_int, _c_vp]),
     "mdetr_fold_weights": (_c_int, [_c_int] + [_c_vp] * 7 + [_c_int, _c_vp]),

@@ -98,6 +98,15 @@ class _AddLayerNorm(torch.autograd.Function):
                                               ctx.seed_dev.data_ptr() if ctx.seed_dev is not None else None, dev, stream)
         if rc != 0:
             _capi.check(rc, "mdetr_add_layernorm_backward")
+        from . import chunk_sums
+        if (chunk_sums.deferring() and (s.is_cuda or chunk_sums._backend is not None) and g_dtype in (torch.float32, torch.bfloat16)
+                and b_dtype in (torch.float32, torch.bfloat16) and chunk_sums.supported(partial[:, :C], g_dtype)):
+            # parameter gradients: nothing reads them before the optimizer, so both sums join the backward pass's grouped launch
+            # (chunk_sums.py) -- two results of their own, each a column half of the one partial set, no slice or cast of a result.
+            # (An alias leaves here: the registration holds the result itself, and AccumulateGrad copies -- reads -- a gradient that
+            # something else still references.)
+            return (da.view(shape), db.view(shape), chunk_sums.chunk_sum(partial[:, :C], g_dtype).view(C),
+                    chunk_sums.chunk_sum(partial[:, C:], b_dtype).view(C), None, None, None, None)
         sums = _column_sum_f32(partial, g_dtype if g_dtype == b_dtype else torch.float32)   # written in the parameters' dtype
         return da.view(shape), db.view(shape), sums[:C].to(g_dtype), sums[C:].to(b_dtype), None, None, None, None
 

@@ -53,23 +53,40 @@ class _Job(ctypes.Structure):
     _fields_ = [("part", ctypes.c_void_p), ("out", ctypes.c_void_p), ("cols", ctypes.c_int64), ("chunks", ctypes.c_int32), ("out_dtype", ctypes.c_int32)]
 
 
+class _PitchedJob(ctypes.Structure):
+    """mdetr_chunk_job_pitched: a column range [chunks, cols] of a wider partial set whose rows are `pitch` floats apart."""
+    _fields_ = [("part", ctypes.c_void_p), ("out", ctypes.c_void_p), ("cols", ctypes.c_int64), ("pitch", ctypes.c_int64), ("chunks", ctypes.c_int32),
+                ("out_dtype", ctypes.c_int32)]
+
+
+def _pitch(part):
+    return part.stride(0) if part.shape[0] > 1 else part.shape[1]
+
+
 def _lib():
     return _backend if _backend is not None else _capi.lib()
 
 
 def supported(part, out_dtype):
-    return ((part.is_cuda or _backend is not None) and part.dim() == 2 and part.dtype == torch.float32 and part.is_contiguous()
-            and part.shape[1] % 4 == 0 and part.shape[0] > 0 and part.data_ptr() % 16 == 0 and out_dtype in (torch.float32, torch.bfloat16))
+    """Contiguous fp32 partials [chunks, cols], or a column range of such a set (``wide[:, c0:c0 + cols]``: unit column stride, rows a
+    multiple of 4 floats apart, the first element 16-byte aligned)."""
+    return ((part.is_cuda or _backend is not None) and part.dim() == 2 and part.dtype == torch.float32 and part.shape[0] > 0
+            and part.shape[1] > 0 and part.shape[1] % 4 == 0 and part.stride(1) == 1 and _pitch(part) % 4 == 0 and _pitch(part) >= part.shape[1]
+            and part.data_ptr() % 16 == 0 and out_dtype in (torch.float32, torch.bfloat16))
 
 
 def _launch(jobs):
-    arr = (_Job * len(jobs))()
+    pitched = any(_pitch(part) != part.shape[1] for part, _ in jobs)
+    arr = ((_PitchedJob if pitched else _Job) * len(jobs))()
     for q, (part, out) in zip(arr, jobs):
         q.part, q.out, q.cols, q.chunks = part.data_ptr(), out.data_ptr(), part.shape[1], part.shape[0]
         q.out_dtype = _capi.MDETR_BF16 if out.dtype == torch.bfloat16 else _capi.MDETR_F32
+        if pitched:
+            q.pitch = _pitch(part)
     dev = jobs[0][0].device
-    rc = _lib().mdetr_chunk_sums(ctypes.cast(arr, ctypes.c_void_p), len(jobs), dev.index if dev.type == "cuda" else -1,
-                                 torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None)
+    entry = _lib().mdetr_chunk_sums_pitched if pitched else _lib().mdetr_chunk_sums
+    rc = entry(ctypes.cast(arr, ctypes.c_void_p), len(jobs), dev.index if dev.type == "cuda" else -1,
+               torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None)
     if rc != 0:
         msg = _lib().mdetr_last_error()
         raise RuntimeError("mdetr_chunk_sums failed (code %d): %s" % (rc, msg.decode() if msg else "?"))
@@ -78,9 +95,11 @@ def _launch(jobs):
 def chunk_sum(part, out_dtype=torch.float32, defer=True):
     """part [chunks, cols] fp32 -> [cols] in out_dtype = the chunks added in order.  Inside ``deferred()`` the values arrive at the
     next ``flush()``; `part` must then be a tensor of its own (not a shared scratch buffer): it is read later.  defer=False: this
-    sum now, whatever the context (its consumer reads it inside the backward pass)."""
+    sum now, whatever the context (its consumer reads it inside the backward pass).  `part` may be a column range of a wider set
+    (the LayerNorm sites' gamma / beta halves, add_ln_ext.py): each range gets a result tensor of its own.  More than 128 chunks
+    are added by 32 row lanes (csrc/colsum.hip); which form a job takes depends on its chunk count alone, deferred or not."""
     if not supported(part, out_dtype):
-        raise RuntimeError("chunk_sum: needs contiguous fp32 partials [chunks, cols], cols a multiple of 4, 16-byte aligned")
+        raise RuntimeError("chunk_sum: needs fp32 partials [chunks, cols] (contiguous, or a column range of such), cols a multiple of 4, 16-byte aligned")
     out = torch.empty(part.shape[1], dtype=out_dtype, device=part.device)
     with _lock:
         if defer and ENABLED and _depth > 0 and not IMMEDIATE:

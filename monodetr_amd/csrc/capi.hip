@@ -709,7 +709,7 @@ int mdetr_head_tail_backward(const float *init_ref, const float *size3d, const f
     return MDETR_OK;
 }
 
-int mdetr_chunk_sums(const mdetr_chunk_job *jobs, int njobs, int device, void *stream)
+int mdetr_chunk_sums_pitched(const mdetr_chunk_job_pitched *jobs, int njobs, int device, void *stream)
 {
     if (njobs == 0) return MDETR_OK;
     const char *why = mdetr::chunk_sums_check(jobs, njobs);
@@ -722,6 +722,18 @@ int mdetr_chunk_sums(const mdetr_chunk_job *jobs, int njobs, int device, void *s
     const hipError_t e = mdetr::chunk_sums_launch(jobs, njobs, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(MDETR_E_HIP, "mdetr_chunk_sums: launch failed: %s", hipGetErrorString(e));
     return MDETR_OK;
+}
+
+int mdetr_chunk_sums(const mdetr_chunk_job *jobs, int njobs, int device, void *stream)
+{
+    if (njobs == 0) return MDETR_OK;
+    if (!jobs || njobs < 0) return fail(MDETR_E_ARG, "mdetr_chunk_sums: no jobs (%d jobs)", njobs);
+    std::vector<mdetr_chunk_job_pitched> wide(static_cast<size_t>(njobs));
+    for (int i = 0; i < njobs; ++i) {
+        const mdetr_chunk_job &q = jobs[i];
+        wide[i] = mdetr_chunk_job_pitched{q.part, q.out, q.cols, q.cols, q.chunks, q.out_dtype};
+    }
+    return mdetr_chunk_sums_pitched(wide.data(), njobs, device, stream);
 }
 
 static int conv3x3_any(const char *who, const void *x, const void *w, const float *shift, const void *mask, void *y, int B, int H, int W, int C, int N,
@@ -1281,6 +1293,31 @@ int mdetr_msda_backward_bf16(const void *value, const int64_t *spatial_shapes, c
                                                           level_start_host, workspace, workspace_bytes,
                                                           static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(MDETR_E_HIP, "mdetr_msda_backward_bf16: launch failed: %s", hipGetErrorString(e));
+    return MDETR_OK;
+}
+
+int mdetr_msda_backward_to(int dtype, int grad_value_dtype, const void *value, const float *loc, const float *attn,
+                           const void *grad_out, void *grad_value, float *grad_loc, float *grad_attn,
+                           int B, int S, int M, int D, int L, int Lq, int P,
+                           const int64_t *spatial_shapes_host, const int64_t *level_start_host,
+                           void *workspace, int64_t workspace_bytes, int device, void *stream)
+{
+    if (int rc = check_common("mdetr_msda_backward_to", MDETR_F32, B, S, M, D, L, Lq, P)) return rc;
+    if ((dtype != MDETR_F32 && dtype != MDETR_BF16) || (grad_value_dtype != MDETR_F32 && grad_value_dtype != MDETR_BF16))
+        return fail(MDETR_E_ARG, "mdetr_msda_backward_to: dtype / grad_value_dtype must be MDETR_F32 or MDETR_BF16 (%d, %d)", dtype, grad_value_dtype);
+    if (!value || !loc || !attn || !grad_out || !grad_value || !grad_loc || !grad_attn)
+        return fail(MDETR_E_ARG, "mdetr_msda_backward_to: null pointer");
+    if (!aligned16(value) || !aligned16(loc) || !aligned16(attn) || !aligned16(grad_out) || !aligned16(grad_value) ||
+        !aligned16(grad_loc) || !aligned16(grad_attn) || !aligned16(workspace))
+        return fail(MDETR_E_ALIGN, "mdetr_msda_backward_to: all tensors must be 16-byte aligned");
+    DeviceScope dev(device);
+    if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "mdetr_msda_backward_to: set device %d: %s", device, hipGetErrorString(dev.err));
+    const hipError_t e = mdetr::msda_backward_to_launch(dtype, grad_value_dtype, value, loc, attn, grad_out, grad_value, grad_loc, grad_attn,
+                                                        B, S, M, D, L, Lq, P, spatial_shapes_host, level_start_host, workspace,
+                                                        workspace_bytes, static_cast<hipStream_t>(stream));
+    if (e == hipErrorNotSupported)
+        return fail(MDETR_E_UNSUPPORTED, "mdetr_msda_backward_to: the one-pass kernel does not take this geometry (B=%d S=%d M=%d D=%d L=%d Lq=%d P=%d)", B, S, M, D, L, Lq, P);
+    if (e != hipSuccess) return fail(MDETR_E_HIP, "mdetr_msda_backward_to: launch failed: %s", hipGetErrorString(e));
     return MDETR_OK;
 }
 

@@ -14,8 +14,9 @@ int64_t colsum_workspace_bytes(int64_t rows, int cols);
 hipError_t colsum_launch(int dtype, const void *x, void *out, void *workspace, int64_t rows, int cols, int64_t ld,
                          hipStream_t st, int out_dtype = 0);
 
-// grouped chunk sums (mdetr_chunk_sums): message or nullptr; any number of jobs (launched kChunkJobs at a time)
-const char *chunk_sums_check(const mdetr_chunk_job *jobs, int njobs);
-hipError_t chunk_sums_launch(const mdetr_chunk_job *jobs, int njobs, hipStream_t st);
+// grouped chunk sums (mdetr_chunk_sums / mdetr_chunk_sums_pitched): message or nullptr; any number of jobs (launched kChunkJobs at
+// a time).  mdetr_chunk_sums hands its jobs over with pitch = cols.
+const char *chunk_sums_check(const mdetr_chunk_job_pitched *jobs, int njobs);
+hipError_t chunk_sums_launch(const mdetr_chunk_job_pitched *jobs, int njobs, hipStream_t st);
 
 }  // namespace mdetr

@@ -119,13 +119,21 @@ void colsum_final_kernel(const float *__restrict__ partial, OT *__restrict__ out
 // all of it fill and drain.  Here ONE launch adds the partials of up to kChunkJobs gradients: the jobs' tables travel as the
 // kernel's argument (copied to LDS once per workgroup), a workgroup owns 1 024 consecutive columns of one job, a thread four
 // of them; the chunks are added in order with four loads in flight.  Same sums, same order, same single rounding.
+//
+// TALL jobs (chunks > kTallChunks: the gamma / beta sums of add_ln.hip's backward, up to 1 024 partial rows x 128 - 512 columns)
+// would be one workgroup walking 256 dependent rounds of loads.  They take a second form: a workgroup owns kTallCols = 32
+// columns and kTallLanes = 32 row lanes, lane r adds chunks r, r + 32, ... in order (four loads in flight), the lanes are added
+// through LDS in lane order.  The form depends on the job's chunk count ALONE -- never on what else shares the launch -- so a sum
+// has the same bits launched singly or grouped; every job of <= kTallChunks chunks is added exactly as before.
+// A job reads columns [0, cols) of rows that are `pitch` floats apart: two results (gamma's and beta's) come from one partial set.
 constexpr int kChunkJobs = 48, kChunkCols = 4 * kThreads;
+constexpr int kTallChunks = 128, kTallLanes = 32, kTallCols = 4 * (kThreads / kTallLanes);
 struct ChunkJob {
     const float *part;
     void *out;
-    int64_t cols;
+    int64_t cols, pitch;
     int chunks, out_bf16;
-    int block0, pad_;
+    int block0, tall;
 };
 struct ChunkArgs {
     ChunkJob j[kChunkJobs];
@@ -136,6 +144,7 @@ __global__ __launch_bounds__(kThreads)
 void chunk_sums_kernel(const ChunkArgs a)
 {
     __shared__ __attribute__((aligned(16))) ChunkArgs la;
+    __shared__ __attribute__((aligned(16))) float red[kTallLanes][kTallCols];
     {
         const unsigned *src = reinterpret_cast<const unsigned *>(&a);
         unsigned *dst = reinterpret_cast<unsigned *>(&la);
@@ -146,22 +155,54 @@ void chunk_sums_kernel(const ChunkArgs a)
     for (int i = 1; i < la.njobs; ++i)
         if (static_cast<int>(blockIdx.x) >= la.j[i].block0) ji = i;
     const ChunkJob &J = la.j[ji];
-    const int64_t cols = J.cols, c = static_cast<int64_t>(static_cast<int>(blockIdx.x) - J.block0) * kChunkCols + 4 * threadIdx.x;
+    const int64_t cols = J.cols, pitch = J.pitch;
+    const int chunks = J.chunks;
+    if (J.tall) {                                              // (uniform over the workgroup: the barrier below is reached by all)
+        const int tc = threadIdx.x % (kTallCols / 4), r = threadIdx.x / (kTallCols / 4);
+        const int64_t c0 = static_cast<int64_t>(static_cast<int>(blockIdx.x) - J.block0) * kTallCols, c = c0 + 4 * tc;
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c < cols) {
+            const float *p = J.part + c;
+            int k = r;
+            for (; k + 3 * kTallLanes < chunks; k += 4 * kTallLanes) {
+                const float4 v0 = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k) * pitch);
+                const float4 v1 = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k + kTallLanes) * pitch);
+                const float4 v2 = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k + 2 * kTallLanes) * pitch);
+                const float4 v3 = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k + 3 * kTallLanes) * pitch);
+                s.x = (((s.x + v0.x) + v1.x) + v2.x) + v3.x; s.y = (((s.y + v0.y) + v1.y) + v2.y) + v3.y;
+                s.z = (((s.z + v0.z) + v1.z) + v2.z) + v3.z; s.w = (((s.w + v0.w) + v1.w) + v2.w) + v3.w;
+            }
+            for (; k < chunks; k += kTallLanes) {
+                const float4 v = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k) * pitch);
+                s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+            }
+        }
+        *reinterpret_cast<float4 *>(&red[r][4 * tc]) = s;
+        __syncthreads();
+        if (threadIdx.x < kTallCols && c0 + threadIdx.x < cols) {
+            float t = 0.f;
+#pragma unroll
+            for (int l = 0; l < kTallLanes; ++l) t += red[l][threadIdx.x];
+            if (J.out_bf16) static_cast<__hip_bfloat16 *>(J.out)[c0 + threadIdx.x] = __float2bfloat16(t);
+            else static_cast<float *>(J.out)[c0 + threadIdx.x] = t;
+        }
+        return;
+    }
+    const int64_t c = static_cast<int64_t>(static_cast<int>(blockIdx.x) - J.block0) * kChunkCols + 4 * threadIdx.x;
     if (c >= cols) return;
     const float *p = J.part + c;
-    const int chunks = J.chunks;
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     int k = 0;
     for (; k + 3 < chunks; k += 4) {
-        const float4 v0 = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k) * cols);
-        const float4 v1 = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k + 1) * cols);
-        const float4 v2 = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k + 2) * cols);
-        const float4 v3 = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k + 3) * cols);
+        const float4 v0 = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k) * pitch);
+        const float4 v1 = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k + 1) * pitch);
+        const float4 v2 = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k + 2) * pitch);
+        const float4 v3 = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k + 3) * pitch);
         s.x = (((s.x + v0.x) + v1.x) + v2.x) + v3.x; s.y = (((s.y + v0.y) + v1.y) + v2.y) + v3.y;
         s.z = (((s.z + v0.z) + v1.z) + v2.z) + v3.z; s.w = (((s.w + v0.w) + v1.w) + v2.w) + v3.w;
     }
     for (; k < chunks; ++k) {
-        const float4 v = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k) * cols);
+        const float4 v = *reinterpret_cast<const float4 *>(p + static_cast<int64_t>(k) * pitch);
         s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
     if (J.out_bf16) {
@@ -172,33 +213,41 @@ void chunk_sums_kernel(const ChunkArgs a)
     }
 }
 
+inline int64_t chunk_job_blocks(const mdetr_chunk_job_pitched &q)
+{
+    const int64_t per = q.chunks > kTallChunks ? kTallCols : kChunkCols;
+    return (q.cols + per - 1) / per;
+}
+
 }  // namespace
 
-const char *chunk_sums_check(const mdetr_chunk_job *jobs, int njobs)
+const char *chunk_sums_check(const mdetr_chunk_job_pitched *jobs, int njobs)
 {
     if (!jobs || njobs <= 0) return "no jobs";
     for (int i = 0; i < njobs; ++i) {
-        const mdetr_chunk_job &q = jobs[i];
+        const mdetr_chunk_job_pitched &q = jobs[i];
         if (!q.part || !q.out || q.cols <= 0 || q.chunks <= 0) return "null pointer or empty job";
         if (q.cols % 4 != 0 || (reinterpret_cast<uintptr_t>(q.part) & 15) != 0) return "cols must be a multiple of 4 and the partials 16-byte aligned";
+        if (q.pitch < q.cols || q.pitch % 4 != 0) return "pitch must be a multiple of 4 and at least cols";
         if (q.out_dtype != 0 && q.out_dtype != 2) return "out_dtype must be MDETR_F32 or MDETR_BF16";
         if ((reinterpret_cast<uintptr_t>(q.out) & (q.out_dtype == 2 ? 7 : 15)) != 0) return "result not aligned (16 bytes fp32, 8 bytes bf16)";
-        if ((q.cols + kChunkCols - 1) / kChunkCols > (1 << 24)) return "job too wide";
+        if (chunk_job_blocks(q) > (1 << 24)) return "job too wide";
     }
     return nullptr;
 }
 
-hipError_t chunk_sums_launch(const mdetr_chunk_job *jobs, int njobs, hipStream_t st)
+hipError_t chunk_sums_launch(const mdetr_chunk_job_pitched *jobs, int njobs, hipStream_t st)
 {
     for (int first = 0; first < njobs; first += kChunkJobs) {
         ChunkArgs a;
         const int n = njobs - first < kChunkJobs ? njobs - first : kChunkJobs;
         int blocks = 0;
         for (int i = 0; i < n; ++i) {
-            const mdetr_chunk_job &q = jobs[first + i];
+            const mdetr_chunk_job_pitched &q = jobs[first + i];
             ChunkJob &J = a.j[i];
-            J.part = q.part; J.out = q.out; J.cols = q.cols; J.chunks = q.chunks; J.out_bf16 = q.out_dtype == 2; J.block0 = blocks; J.pad_ = 0;
-            blocks += static_cast<int>((q.cols + kChunkCols - 1) / kChunkCols);
+            J.part = q.part; J.out = q.out; J.cols = q.cols; J.pitch = q.pitch; J.chunks = q.chunks; J.out_bf16 = q.out_dtype == 2; J.block0 = blocks;
+            J.tall = q.chunks > kTallChunks;
+            blocks += static_cast<int>(chunk_job_blocks(q));
         }
         a.njobs = n; a.pad_ = 0;
         hipLaunchKernelGGL(chunk_sums_kernel, dim3(blocks), dim3(kThreads), 0, st, a);

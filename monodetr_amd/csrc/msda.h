@@ -87,9 +87,17 @@ hipError_t msda_tiled_grad_value_launch(const int64_t *shapes_h, const int64_t *
 // with few queries; D = 32.  elem_dtype 0: value / grad_out fp32, 2: bf16.  Writes every output completely.
 int64_t msda_fused_workspace_bytes(const int64_t *shapes_h, const int64_t *start_h, int B, int S, int M, int D, int L, int Lq, int P);
 hipError_t msda_backward_fused_launch(const int64_t *shapes_h, const int64_t *start_h, const void *value, const float *loc,
-                                      const float *attn, const void *grad_out, float *grad_value, float *grad_loc, float *grad_attn,
+                                      const float *attn, const void *grad_out, void *grad_value, float *grad_loc, float *grad_attn,
                                       void *workspace, int64_t workspace_bytes, int B, int S, int M, int D, int L, int Lq, int P,
-                                      int elem_dtype, hipStream_t st);
+                                      int elem_dtype, hipStream_t st, int gv_dtype = 0 /* grad_value alone: 0 = f32, 2 = bf16 */);
+// The one-pass backward with grad_value written as gv_dtype (0 = f32, 2 = bf16) -- the type its consumer reads -- for fp32
+// (elem_dtype 0) or bf16 (2) value / grad_out.  No other strategy writes bf16: hipErrorNotSupported where the geometry does not
+// qualify, and nothing has been written then.
+hipError_t msda_backward_to_launch(int elem_dtype, int gv_dtype, const void *value, const float *loc, const float *attn,
+                                   const void *grad_out, void *grad_value, float *grad_loc, float *grad_attn,
+                                   int B, int S, int M, int D, int L, int Lq, int P,
+                                   const int64_t *shapes_host, const int64_t *lstart_host,
+                                   void *workspace, int64_t workspace_bytes, hipStream_t st);
 
 // msda_cpu.hip: host implementation (every pointer a HOST pointer); dtype 0 = f32, 1 = f64
 void msda_forward_cpu(int dtype, const void *value, const int64_t *shapes, const int64_t *lstart, const void *loc,

@@ -923,6 +923,20 @@ hipError_t msda_backward_bf16_launch(const void *value, const int64_t *shapes, c
     return hipGetLastError();
 }
 
+hipError_t msda_backward_to_launch(int elem_dtype, int gv_dtype, const void *value, const float *loc, const float *attn,
+                                   const void *grad_out, void *grad_value, float *grad_loc, float *grad_attn,
+                                   int B, int S, int M, int D, int L, int Lq, int P,
+                                   const int64_t *shapes_host, const int64_t *lstart_host,
+                                   void *workspace, int64_t workspace_bytes, hipStream_t st)
+{
+    const int bwd_env = [] { char tb[16]; const char *ev = tune_str("msda_bwd", tb, sizeof(tb)); return !ev || !*ev || ev[0] == 'f' ? 0 : (ev[0] == 't' ? 1 : 2); }();
+    if (bwd_env != 0 || (elem_dtype != 0 && elem_dtype != 2) || !msda_fast_path(0, D, L, P) || (elem_dtype == 2 && (L != 4 || P != 4)) ||
+        static_cast<int64_t>(B) * Lq * M == 0 || !shapes_host || !lstart_host || !workspace)
+        return hipErrorNotSupported;
+    return msda_backward_fused_launch(shapes_host, lstart_host, value, loc, attn, grad_out, grad_value, grad_loc, grad_attn,
+                                      workspace, workspace_bytes, B, S, M, D, L, Lq, P, elem_dtype, st, gv_dtype);
+}
+
 hipError_t msda_backward_launch(int dtype, const void *value, const int64_t *shapes, const int64_t *lstart,
                                 const void *loc, const void *attn, const void *grad_out,
                                 void *grad_value, void *grad_loc, void *grad_attn,

@@ -96,7 +96,19 @@ struct FusedPlan {
     int max_tab;                      // ints of the centre-cell tables a mode-0 block may need
     int npre;                         // workgroups of the pre-pass = pairs of maxima behind the workspace header
     int small;                        // every extent < 2^13: the rectangle bounds and chunk limits fit 32-bit arithmetic
+    int gv_bf16;                      // grad_value is bf16 (the type its consumer, a bf16 token GEMM, reads): core tiles round their
+                                      // fp32 pair once and store 4 bytes, the finalize pass writes bf16; scratch / `far` stay fp32
 };
+
+// two fp32 values -> a bf16 pair (round to nearest even, each once), low half first
+__device__ __forceinline__ unsigned bf16x2_rne(float a, float b)
+{
+    const __hip_bfloat16 x = __float2bfloat16(a), y = __float2bfloat16(b);
+    unsigned short ux, uy;
+    __builtin_memcpy(&ux, &x, 2);
+    __builtin_memcpy(&uy, &y, 2);
+    return static_cast<unsigned>(ux) | (static_cast<unsigned>(uy) << 16);
+}
 
 // ---- tiny helpers ---------------------------------------------------------------------------------
 __host__ __device__ inline int ceil_div_ll(long long a, long long b)   // b > 0, any sign of a
@@ -883,7 +895,7 @@ void msda_bwd_fused(const FusedPlan pl, const VT *__restrict__ value, const floa
             const unsigned long long cbits = static_cast<unsigned long long>(__builtin_bit_cast(unsigned, magic)) * 0x100000001ull;
             const float inv = finite ? ldexpf(1.0f, -(22 - shift - e)) : 0.f;
             float *dst1 = scratch + (static_cast<int64_t>(b) * M + m) * pl.scr_per_bm + pl.scr0[l] + static_cast<int64_t>(w.slot) * w.ncell * kCH;
-            float *dst0 = grad_value + ((static_cast<int64_t>(b) * pl.S + pl.start[l]) * M + m) * kCH;
+            float *dst0 = grad_value + ((static_cast<int64_t>(b) * pl.S + pl.start[l]) * M + m) * (pl.gv_bf16 ? kCH / 2 : kCH);   // (bf16: two per word)
             unsigned mc = 0u;
             for (int i = threadIdx.x; i < w.ncell * kCellU64; i += THREADS) {
                 const int cell = i / kCellU64, pr = i % kCellU64;
@@ -908,8 +920,10 @@ void msda_bwd_fused(const FusedPlan pl, const VT *__restrict__ value, const floa
                 } else {
                     const int wxx = cell % w.tstride;
                     const int yy = w.cy0 + cell / w.tstride, xx = w.cx0 + wxx;
-                    if (yy < H && xx < W && wxx < pl.TW[l])   // cores partition the level: exclusive owner, plain store (not the padding column)
-                        *reinterpret_cast<float2 *>(dst0 + static_cast<int64_t>(yy * W + xx) * (M * kCH) + 2 * pr) = out;
+                    if (yy < H && xx < W && wxx < pl.TW[l]) { // cores partition the level: exclusive owner, plain store (not the padding column)
+                        if (pl.gv_bf16) dst0[static_cast<int64_t>(yy * W + xx) * (M * kCH / 2) + pr] = __uint_as_float(bf16x2_rne(out.x, out.y));
+                        else *reinterpret_cast<float2 *>(dst0 + static_cast<int64_t>(yy * W + xx) * (M * kCH) + 2 * pr) = out;
+                    }
                 }
             }
             if (OWNER) break;
@@ -954,6 +968,9 @@ __device__ __forceinline__ void finalize_row(const FusedPlan &pl, const float *_
             for (int u = 0; u < kFlight; ++u)
                 if (t0 + u < nch) { acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w; }
         }
+    } else if (pl.gv_bf16) {                                 // (only with use_far) the core tile's rounded value: rounded again below
+        const uint2 h = *reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(grad_value) + row * kCH + c4);
+        acc = make_float4(__uint_as_float(h.x << 16), __uint_as_float(h.x & 0xFFFF0000u), __uint_as_float(h.y << 16), __uint_as_float(h.y & 0xFFFF0000u));
     } else {
         acc = *reinterpret_cast<const float4 *>(grad_value + row * kCH + c4);
     }
@@ -963,7 +980,10 @@ __device__ __forceinline__ void finalize_row(const FusedPlan &pl, const float *_
         acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
         *f = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    *reinterpret_cast<float4 *>(grad_value + row * kCH + c4) = acc;
+    if (pl.gv_bf16)
+        *reinterpret_cast<uint2 *>(reinterpret_cast<unsigned short *>(grad_value) + row * kCH + c4) = make_uint2(bf16x2_rne(acc.x, acc.y), bf16x2_rne(acc.z, acc.w));
+    else
+        *reinterpret_cast<float4 *>(grad_value + row * kCH + c4) = acc;
 }
 
 __global__ __launch_bounds__(256)
@@ -1160,15 +1180,19 @@ int64_t msda_fused_workspace_bytes(const int64_t *shapes_h, const int64_t *start
 
 // value_dtype / grad_dtype: 0 = f32, 2 = bf16.  Writes all three outputs completely (no pre-zeroing needed).  Returns
 // hipErrorNotSupported when the geometry does not qualify (the caller falls back to the atomic path).
+// gv_dtype: the type of grad_value alone (0 = f32, 2 = bf16), whatever elem_dtype is: B * S * M * D elements of it.
 hipError_t msda_backward_fused_launch(const int64_t *shapes_h, const int64_t *start_h, const void *value, const float *loc,
-                                      const float *attn, const void *grad_out, float *grad_value, float *grad_loc, float *grad_attn,
+                                      const float *attn, const void *grad_out, void *grad_value_any, float *grad_loc, float *grad_attn,
                                       void *workspace, int64_t workspace_bytes, int B, int S, int M, int D, int L, int Lq, int P,
-                                      int elem_dtype, hipStream_t st)
+                                      int elem_dtype, hipStream_t st, int gv_dtype)
 {
     FusedPlan pl;
     if (D != kCH || !shapes_h || !start_h || !build_plan(pl, shapes_h, start_h, B, S, M, L, Lq, P, elem_dtype)) return hipErrorNotSupported;
     if (!workspace || workspace_bytes < plan_workspace_bytes(pl)) return hipErrorNotSupported;
     if (elem_dtype != 0 && elem_dtype != 2) return hipErrorNotSupported;
+    if (gv_dtype != 0 && gv_dtype != 2) return hipErrorNotSupported;
+    pl.gv_bf16 = gv_dtype == 2;
+    float *grad_value = static_cast<float *>(grad_value_any);   // (bf16 when pl.gv_bf16: the kernels index it accordingly)
     Header *hdr = static_cast<Header *>(workspace);
     const int64_t nfar = static_cast<int64_t>(B) * S * M * kCH;
     // candidate scheme: [kHdrBytes, kHdrBytes + 4 nfar) = the side buffer, zero between calls, then the partial windows; owner scheme: neither

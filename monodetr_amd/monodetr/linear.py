@@ -40,6 +40,30 @@ _TWGRAD_MIN_ROWS = 1024
 _PREMASK = os.environ.get("MDETR_RELU_PREMASK") == "1"
 
 
+class WideGradToken:
+    """The contract between the producer of an fp32 `wide_out` result y (bf16 operands: the value projection of the decoder's
+    deformable cross-attention) and its ONE consumer, the fp32 MSDA operator.  The producer's backward rounds the arriving fp32
+    gradient to bf16 before its products; the operator's kernel can write that gradient in bf16 itself (the same rounding, one
+    launch and 126 MB of traffic less per call).  Autograd converts a gradient to its tensor's dtype on the way out of a node, so
+    the bf16 tensor cannot travel as the gradient: the producer hangs a token on y (`y._mdetr_wide_token`) and keeps it, the
+    operator's backward leaves its bf16 value gradient in `grad` and returns no gradient for y, the producer's backward takes it
+    from there (and adds whatever another consumer sent the ordinary way).  The module hands the token to the operator only where
+    nothing sits between the two (no padding mask): monodetr/ops/modules/ms_deform_attn.py."""
+    __slots__ = ("grad",)
+
+    def __init__(self):
+        self.grad = None
+
+    def take(self, dy, shape, dtype):
+        """The gradient of y for the producer's backward, in `dtype` (the operands'): the token's, the arriving one rounded once,
+        their sum, or None."""
+        g, self.grad = self.grad, None
+        if g is None:
+            return dy.to(dtype) if dy is not None else None
+        g = g.view(shape)
+        return g.to(dtype) if dy is None else (dy + g.float()).to(dtype)
+
+
 class ReluToken:
     """The contract between the producer of a ReLU output y and its ONE consumer.  The producer hangs a token on y
     (`y._mdetr_relu_token`) and keeps it; a consumer whose backward applies the ReLU's mask to the input gradient it returns (y <= 0 ->
@@ -224,16 +248,23 @@ class _TokenLinearSkip(torch.autograd.Function):
             ctx.save_for_backward(q, weight, y)
         else:
             ctx.save_for_backward(q, weight)
+        ctx.wide_token = None
+        if ctx.wide_out:
+            ctx.wide_token = y._mdetr_wide_token = WideGradToken()
+            ctx.set_materialize_grads(False)                         # (the consumer may leave its gradient in the token: y's arrives as None)
         return y, x.view_as(x)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy, dskip):
         q, weight = ctx.saved_tensors[:2]
+        if ctx.wide_out:
+            # one rounding of the fp32 gradient, as the narrow form receives it -- here, or already in the consumer's kernel
+            dy = ctx.wide_token.take(dy, q.shape[:-1] + (weight.shape[0],), q.dtype)
+            if dy is None:                                             # y went unused
+                return (dskip if ctx.needs_input_grad[0] else None), None, None, None, None, None, None, None, None
         if ctx.relu and not (ctx.out_token is not None and ctx.out_token.premasked and ctx.scale == 1.0):
             dy = _act_backward(dy.contiguous(), ctx.saved_tensors[2], ctx.scale)       # (premasked: the gradient arrived masked)
-        if ctx.wide_out:
-            dy = dy.to(q.dtype)                                        # one rounding of the fp32 gradient, as the narrow form receives it
         q2, dy2 = q.reshape(-1, q.shape[-1]), dy.reshape(-1, dy.shape[-1])
         dx = None
         if ctx.needs_input_grad[0]:
@@ -286,6 +317,7 @@ class _TokenLinear(torch.autograd.Function):
         ctx.bias_dtype = bias.dtype if bias is not None else None
         ctx.fused_relu = False
         ctx.wide_out = bool(wide_out)
+        ctx.wide_token = None
         ctx.scale = 1.0 / (1.0 - dropout_p) if dropout_p > 0.0 else 1.0
         x2 = x.reshape(-1, x.shape[-1])
         if _tgemm_ok(x2, weight, bias):
@@ -297,6 +329,9 @@ class _TokenLinear(torch.autograd.Function):
                 ctx.save_for_backward(x, weight, y)
             else:
                 ctx.save_for_backward(x, weight)
+            if ctx.wide_out:
+                ctx.wide_token = y._mdetr_wide_token = WideGradToken()
+                ctx.set_materialize_grads(False)                     # (the consumer may leave its gradient in the token: y's arrives as None)
             return y
         if dropout_p > 0.0:
             raise RuntimeError("token_linear: dropout is only fused into csrc/tgemm.hip's epilogue")
@@ -323,7 +358,10 @@ class _TokenLinear(torch.autograd.Function):
         else:
             x, weight = ctx.saved_tensors
         if ctx.wide_out:
-            dy = dy.to(x.dtype)                                        # one rounding of the fp32 gradient, as the narrow form receives it
+            # one rounding of the fp32 gradient, as the narrow form receives it -- here, or already in the consumer's kernel
+            dy = ctx.wide_token.take(dy, x.shape[:-1] + (weight.shape[0],), x.dtype) if ctx.wide_token is not None else dy.to(x.dtype)
+            if dy is None:                                             # y went unused
+                return None, None, None, None, None, None
         dx = dw = db = None
         x2 = x.reshape(-1, x.shape[-1])
         dy2 = dy.reshape(-1, dy.shape[-1])

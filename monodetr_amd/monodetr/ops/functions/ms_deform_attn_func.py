@@ -29,6 +29,14 @@ _LOW = (torch.bfloat16, torch.float16)
 # (include/monodetr_amd.h, mdetr_msda_forward_bf16) instead of being widened to fp32 around the call.  Off until the
 # kernels have run on the GPU.
 _NATIVE_BF16 = os.environ.get("MDETR_MSDA_BF16") == "1"
+# (tests: False = the fp32 value gradient and its conversion, what the bf16 form is compared with bit for bit)
+_BF16_GRAD_VALUE = True
+
+
+def _takes_grad_value_dtype():
+    """Does the extension-module object write grad_value in a type of the caller's choice?  (msda_ext does; an object substituted
+    for it -- the reference's module, a test's stand-in -- need not know the argument.)"""
+    return bool(getattr(MSDA, "GRAD_VALUE_DTYPE", False))
 
 
 class MSDeformAttnFunction(Function):
@@ -38,8 +46,11 @@ class MSDeformAttnFunction(Function):
     # back in the dtypes of the corresponding inputs.
     @staticmethod
     def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_locations,
-                attention_weights, im2col_step):
+                attention_weights, im2col_step, value_token=None):
+        # value_token (not in the reference's signature; monodetr/linear.py WideGradToken): the producer of an fp32 `value` whose
+        # backward wants the value gradient in bf16 -- the kernel writes it so and it travels in the token
         ctx.im2col_step = im2col_step
+        ctx.value_token = value_token if (_BF16_GRAD_VALUE and _takes_grad_value_dtype() and value.dtype == torch.float32) else None
         ctx.in_dtypes = (value.dtype, sampling_locations.dtype, attention_weights.dtype)
         ctx.native_bf16 = _NATIVE_BF16 and value.dtype == torch.bfloat16 and MSDA.bf16_supported(value, sampling_locations)
         if ctx.native_bf16:
@@ -66,12 +77,20 @@ class MSDeformAttnFunction(Function):
         value, shapes, level_start, loc, attn = ctx.saved_tensors
         dv, dl, da = ctx.in_dtypes
         if ctx.native_bf16:
+            # (dv is bf16 here: the kernels write the value gradient in the type its consumer -- the value projection's bf16 products --
+            # reads, the fp32 sums rounded once, instead of an fp32 tensor and a cast launch)
+            kw = {"grad_value_dtype": dv} if _BF16_GRAD_VALUE and _takes_grad_value_dtype() else {}
             g_value, g_loc, g_attn = MSDA.ms_deform_attn_backward_bf16(
-                value, shapes, level_start, loc, attn, grad_output.to(torch.bfloat16).contiguous())
-            return g_value.to(dv), None, None, g_loc.to(dl), g_attn.to(da), None
+                value, shapes, level_start, loc, attn, grad_output.to(torch.bfloat16).contiguous(), **kw)
+            return g_value.to(dv), None, None, g_loc.to(dl), g_attn.to(da), None, None
+        if ctx.value_token is not None and not ctx.native_bf16 and value.dtype == torch.float32 and dv == torch.float32:
+            g_value, g_loc, g_attn = MSDA.ms_deform_attn_backward(
+                value, shapes, level_start, loc, attn, grad_output.to(value.dtype).contiguous(), ctx.im2col_step, grad_value_dtype=torch.bfloat16)
+            ctx.value_token.grad = g_value
+            return None, None, None, g_loc.to(dl), g_attn.to(da), None, None
         g_value, g_loc, g_attn = MSDA.ms_deform_attn_backward(
             value, shapes, level_start, loc, attn, grad_output.to(value.dtype).contiguous(), ctx.im2col_step)
-        return g_value.to(dv), None, None, g_loc.to(dl), g_attn.to(da), None
+        return g_value.to(dv), None, None, g_loc.to(dl), g_attn.to(da), None, None
 
 
 def ms_deform_attn_core_pytorch(value, value_spatial_shapes, sampling_locations, attention_weights):

@@ -111,6 +111,9 @@ class MSDeformAttn(nn.Module):
             value, input_next = token_linear_skip(input_flatten, self.value_proj.weight, self.value_proj.bias, wide_out=wide)
         else:
             value, input_next = token_linear(input_flatten, self.value_proj.weight, self.value_proj.bias, wide_out=wide), input_flatten
+        # (the wide form's producer can take its bf16 gradient straight from the operator's kernel: linear.WideGradToken -- only
+        # where the operator is the projection's direct consumer)
+        value_token = getattr(value, "_mdetr_wide_token", None) if wide and input_padding_mask is None else None
         if input_padding_mask is not None:
             value = value.masked_fill(input_padding_mask[..., None], 0.0)
         value = value.view(N, S, M, -1)
@@ -124,7 +127,8 @@ class MSDeformAttn(nn.Module):
         else:
             offsets = token_linear(query, self.sampling_offsets.weight, self.sampling_offsets.bias).view(N, Lq, M, L, P, 2)
             logits = token_linear(query, self.attention_weights.weight, self.attention_weights.bias).view(N, Lq, M, L * P)
-        out = self._attend(value, packed, offsets, logits, reference_points, input_spatial_shapes, input_level_start_index, query.dtype)
+        out = self._attend(value, packed, offsets, logits, reference_points, input_spatial_shapes, input_level_start_index, query.dtype,
+                           value_token)
         return (out, input_next) if chain_input else out
 
     def _packed_projection(self):
@@ -133,7 +137,8 @@ class MSDeformAttn(nn.Module):
         return (torch.cat((self.sampling_offsets.weight, self.attention_weights.weight), 0),
                 torch.cat((self.sampling_offsets.bias, self.attention_weights.bias), 0))
 
-    def _attend(self, value, packed, offsets, logits, reference_points, input_spatial_shapes, input_level_start_index, out_dtype):
+    def _attend(self, value, packed, offsets, logits, reference_points, input_spatial_shapes, input_level_start_index, out_dtype,
+                value_token=None):
         N, S = value.shape[:2]
         M, L, P = self.n_heads, self.n_levels, self.n_points
         Lq = (packed if packed is not None else offsets).shape[1]
@@ -156,7 +161,7 @@ class MSDeformAttn(nn.Module):
                 locations = ref[..., :2] + offsets / P * extent * 0.5
 
         out = MSDeformAttnFunction.apply(value, input_spatial_shapes, input_level_start_index,
-                                         locations, weights, self.im2col_step)
+                                         locations, weights, self.im2col_step, value_token)
         out = _cut.at("msda", out, when_armed=True)                   # (a two-graph iteration may start its second graph here)
         if out.dtype != out_dtype and out_dtype == torch.bfloat16:
             out = out.to(out_dtype)                                    # (the fp32 operator of the wide form)

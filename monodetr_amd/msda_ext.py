@@ -24,6 +24,8 @@ _NAMES5 = ("value", "spatial_shapes", "level_start_index", "sampling_loc", "attn
 # cpu/ms_deform_attn_cpu.cpp:26,39) and so does this module -- the switch exists so that BASELINE configs[0] (the yaml on a
 # CPU, one training iteration: plumbing) can run at all.  CUDA tensors never take this route, switch or no switch.
 _ALLOW_CPU = False
+# the two backward functions take ``grad_value_dtype`` (not in the reference's module; MSDeformAttnFunction asks before it passes one)
+GRAD_VALUE_DTYPE = True
 
 
 def allow_cpu(on=True):
@@ -99,6 +101,30 @@ def _workspace(device, nbytes):
     return W.get("msda", device, nbytes, zero=True)
 
 
+def _backward_to(code, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, dims, grad_value_dtype):
+    """mdetr_msda_backward_to: the one-pass backward writing grad_value as `grad_value_dtype` (the type its consumer reads) -> the three
+    gradients, or None where that kernel does not take the geometry (nothing has been written then)."""
+    B, S, M, D, L, Lq, P = dims
+    if B * Lq == 0 or D != 32:
+        return None
+    lib = _capi.lib()
+    sh_h, st_h = _geometry_on_host(spatial_shapes, level_start_index)
+    ws_bytes = lib.mdetr_msda_backward_workspace_bytes(_capi.MDETR_F32, sh_h.data_ptr(), st_h.data_ptr(), B, S, M, D, L, Lq, P)
+    if ws_bytes <= 0:
+        return None
+    ws = _workspace(value.device, ws_bytes)
+    grad_value = torch.empty(value.shape, dtype=grad_value_dtype, device=value.device)      # written completely by the kernels
+    grad_loc, grad_attn = torch.empty_like(sampling_loc), torch.empty_like(attn_weight)
+    rc = lib.mdetr_msda_backward_to(code, _capi.MDETR_BF16 if grad_value_dtype == torch.bfloat16 else _capi.MDETR_F32, value.data_ptr(),
+                                    sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(), grad_value.data_ptr(),
+                                    grad_loc.data_ptr(), grad_attn.data_ptr(), B, S, M, D, L, Lq, P, sh_h.data_ptr(), st_h.data_ptr(),
+                                    ws.data_ptr(), ws_bytes, value.device.index, _stream(value.device))
+    if rc == _capi.MDETR_E_UNSUPPORTED:
+        return None
+    _capi.check(rc, "mdetr_msda_backward_to")
+    return [grad_value, grad_loc, grad_attn]
+
+
 def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step):
     """-> Tensor [B, Lq, M*D]  (ms_deform_attn_cuda.cu:20-80)."""
     args = (value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
@@ -118,8 +144,10 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     return out
 
 
-def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step):
-    """-> [grad_value, grad_sampling_loc, grad_attn_weight]  (ms_deform_attn_cuda.cu:83-153)."""
+def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step, grad_value_dtype=None):
+    """-> [grad_value, grad_sampling_loc, grad_attn_weight]  (ms_deform_attn_cuda.cu:83-153).
+    grad_value_dtype (not in the reference's signature): torch.bfloat16 = grad_value of fp32 tensors written in bf16, the fp32 result
+    rounded once (its consumer is a bf16 product); by the one-pass kernel where it takes the geometry, by a conversion otherwise."""
     args = (value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
     if _ALLOW_CPU and not value.is_cuda:
         return _backward_cpu(*args, grad_output, im2col_step)
@@ -129,6 +157,14 @@ def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_l
         raise RuntimeError("grad_output must be [B,Lq,M*D] of value's dtype")
     code = _capi.dtype_code(value)
     value, sampling_loc, attn_weight, grad_output = (_aligned(t) for t in (value, sampling_loc, attn_weight, grad_output))
+    if grad_value_dtype is not None and grad_value_dtype != value.dtype:
+        if grad_value_dtype != torch.bfloat16 or code != _capi.MDETR_F32:
+            raise RuntimeError("grad_value_dtype: torch.bfloat16 beside float32 tensors only")
+        got = _backward_to(code, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, (B, S, M, D, L, Lq, P), grad_value_dtype)
+        if got is None:
+            got = ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, im2col_step)
+            got[0] = got[0].to(grad_value_dtype)
+        return got
     grad_value = torch.empty_like(value)                  # written completely (or zero-filled first) by the C ABI on the stream
     grad_loc = torch.empty_like(sampling_loc)
     grad_attn = torch.empty_like(attn_weight)
@@ -230,14 +266,23 @@ def ms_deform_attn_forward_bf16(value, spatial_shapes, level_start_index, sampli
     return out
 
 
-def ms_deform_attn_backward_bf16(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output):
-    """-> [grad_value, grad_sampling_loc, grad_attn_weight], all fp32, from bf16 ``value`` / ``grad_output``."""
+def ms_deform_attn_backward_bf16(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, grad_value_dtype=torch.float32):
+    """-> [grad_value, grad_sampling_loc, grad_attn_weight], all fp32, from bf16 ``value`` / ``grad_output``.
+    grad_value_dtype=torch.bfloat16: grad_value in bf16 -- the fp32 result rounded once -- for a consumer that reads bf16."""
     args = (value, spatial_shapes, level_start_index, sampling_loc, attn_weight)
     _check_inputs(args + (grad_output,), _NAMES5 + ("grad_output",))
     B, S, M, D, L, Lq, P = _dims_mixed(*args)
     if grad_output.dtype != torch.bfloat16 or grad_output.numel() != B * Lq * M * D:
         raise RuntimeError("grad_output must be bfloat16 [B,Lq,M*D]")
     value, sampling_loc, attn_weight, grad_output = (_aligned(t) for t in (value, sampling_loc, attn_weight, grad_output))
+    if grad_value_dtype != torch.float32:
+        if grad_value_dtype != torch.bfloat16:
+            raise RuntimeError("grad_value_dtype must be torch.float32 or torch.bfloat16")
+        got = _backward_to(_capi.MDETR_BF16, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, (B, S, M, D, L, Lq, P), grad_value_dtype)
+        if got is None:
+            got = ms_deform_attn_backward_bf16(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output)
+            got[0] = got[0].to(grad_value_dtype)
+        return got
     grad_value = torch.empty(value.shape, dtype=torch.float32, device=value.device)   # zero-filled by the C ABI
     grad_loc = torch.empty_like(sampling_loc)
     grad_attn = torch.empty_like(attn_weight)
