@@ -27,8 +27,20 @@
 //     significand bits (2^-16 per product): the self-attention q / k projection gradients, which pass
 //     through the ill-conditioned softmax Jacobian, came out at 3e-3 .. 6e-3 of float64, above the
 //     1e-3 bar of the fp32 path.  fp32 accumulation in both modes; exp2-domain online
-//     softmax with the scale folded into Q (or K), dropout on the probabilities from a stateless
+//     softmax with the scale folded into Q, dropout on the probabilities from a stateless
 //     counter hash of (seed, b, h, q, k) so forward and backward regenerate the same mask.
+//
+// Rounding model (what tests/attn_cases.py restates in fp64).  c = fl32(scale * log2e).
+//   * ONE scaled operand, q' = fl32(q c) -- rounded to bf16 in bf16 mode, split exactly in fp32 mode -- in all three
+//     kernels; k enters as it is.  The forward, dQ and dK/dV kernels therefore see the SAME log2-domain scores
+//     s = q' k, and the backward's P = exp2(s - lse) with the forward's lse are the forward's probabilities.  (Until
+//     this was made so the dK/dV kernel rounded k c instead: at a logit standard deviation of 8 its rows of P summed to
+//     0.95 .. 1.05 and dK / dV were 1.7 % / 2.0 % off, against 0.5 % for the roundings below.)
+//   * forward: e = exp2(s - running max) is rounded to bf16 (after the drop) for the product with v; l sums the
+//     unrounded e, dropped ones included; out = acc (rinv / l), rounded once at the store; lse = max + log2 l in fp32.
+//   * backward: D = rowsum(dO out) from the stored (rounded) out; P keep and dS = P (dP keep rinv - D) are rounded to
+//     bf16 for their products; dQ = scale (dS k), dK = (dS^T q') / log2e, dV = rinv (P keep)^T dO, each rounded once at
+//     the store.  In fp32 mode every "rounded to bf16" reads "split into three bf16 parts": fp32 throughout.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -47,7 +59,7 @@ constexpr int kTile = 64;          // rows of a staged K/V (or Q/dO) tile
 constexpr int kRowPad = 40;        // bf16 per row of a row-major tile (80 B: 16-B aligned, spreads banks)
 constexpr int kTPad = 68;          // bf16 per row of a transposed tile [d][64 rows + 4]: 34 dwords per row = 2 x odd, so the 32 lanes of a
                                    // ds_read_b64 group (and the 16 of a ds_read2_b64 group) hit 64 (32) distinct banks; 72 was 2-way (PMC: 52 % conflict cycles)
-constexpr float kLog2e = 1.4426950408889634f;
+constexpr float kLog2e = 1.4426950408889634f, kInvLog2e = 0.6931471805599453f;
 
 struct AttnArgs {
     const void *q, *k, *v;         // [B, L, H*32] with row strides (elements); last dim contiguous
@@ -212,8 +224,9 @@ __device__ __forceinline__ Raw8<T> tile_load(const T *base, int row_stride, int 
     return r;
 }
 
+// `mul` scales the elements before they are rounded / split (the dK/dV kernel's Q tile: scale * log2e, as own_row_frags)
 template <typename T, bool RM, bool TR, bool SP>
-__device__ __forceinline__ void tile_store(const Raw8<T> &raw, __bf16 *rm, __bf16 *tr)
+__device__ __forceinline__ void tile_store(const Raw8<T> &raw, __bf16 *rm, __bf16 *tr, float mul = 1.f)
 {
 #if MDETR_ATTN_STAGE_REMAP
     const int t = threadIdx.x & 255, row = (t & 15) + 16 * (t >> 6), dc = ((t >> 4) & 3) * 8;
@@ -225,8 +238,8 @@ __device__ __forceinline__ void tile_store(const Raw8<T> &raw, __bf16 *rm, __bf1
     bf16x8 vh, vm, vl;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        if (SP) { const HiLo s2 = split_bf16(x[i]); vh[i] = s2.h; vm[i] = s2.m; vl[i] = s2.l; }
-        else vh[i] = static_cast<__bf16>(x[i]);
+        if (SP) { const HiLo s2 = split_bf16(x[i] * mul); vh[i] = s2.h; vm[i] = s2.m; vl[i] = s2.l; }
+        else vh[i] = static_cast<__bf16>(x[i] * mul);
     }
     if (RM) {
         *reinterpret_cast<bf16x8 *>(rm + row * kRowPad + dc) = vh;
@@ -611,7 +624,10 @@ void attn_bwd_dkv_kernel(const AttnArgs a, const T *__restrict__ d_o, const floa
     const float *Db = dsum + (static_cast<int64_t>(b) * a.H + h) * a.Lq;
 
     Frag kf[2], vf[2];
-    own_row_frags<T, SP>(K + static_cast<int64_t>(key) * a.k_rs, kv, a.scale * kLog2e, lane, kf);
+    // The scores must be the forward's (its lse is subtracted from them): the scaled and rounded operand is Q, as in the forward
+    // and dQ kernels -- the Q tile is scaled on its way into LDS, K enters as it is, and dK = Q'^T dS / log2e with Q' = Q scale log2e.
+    const float qmul = a.scale * kLog2e;
+    own_row_frags<T, SP>(K + static_cast<int64_t>(key) * a.k_rs, kv, 1.f, lane, kf);
     own_row_frags<T, SP>(V + static_cast<int64_t>(key) * a.v_rs, kv, 1.f, lane, vf);
     bool key_ok = kv;
     if (a.kpm && kv) key_ok = a.kpm[static_cast<int64_t>(b) * a.Lk + key] == 0;
@@ -632,7 +648,7 @@ void attn_bwd_dkv_kernel(const AttnArgs a, const T *__restrict__ d_o, const floa
     }
     for (int q0 = 0; q0 < a.Lq; q0 += kTile) {
         __syncthreads();
-        tile_store<T, true, true, SP>(rq, Qs, Qt);
+        tile_store<T, true, true, SP>(rq, Qs, Qt, qmul);
         tile_store<T, true, true, SP>(ro, Os, Ot);
         if (threadIdx.x < kTile) {
             Ls[threadIdx.x] = rl; Ds[threadIdx.x] = rd;
@@ -686,7 +702,7 @@ void attn_bwd_dkv_kernel(const AttnArgs a, const T *__restrict__ d_o, const floa
         const int64_t row = (static_cast<int64_t>(b) * a.Lk + key) * (a.H * kD) + h * kD + 4 * half;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            store4<T>(dk + row + 8 * g, acck[4 * g] * a.scale, acck[4 * g + 1] * a.scale, acck[4 * g + 2] * a.scale, acck[4 * g + 3] * a.scale);
+            store4<T>(dk + row + 8 * g, acck[4 * g] * kInvLog2e, acck[4 * g + 1] * kInvLog2e, acck[4 * g + 2] * kInvLog2e, acck[4 * g + 3] * kInvLog2e);
             store4<T>(dv + row + 8 * g, accv[4 * g] * rinv, accv[4 * g + 1] * rinv, accv[4 * g + 2] * rinv, accv[4 * g + 3] * rinv);
         }
     }
