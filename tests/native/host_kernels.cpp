@@ -132,6 +132,7 @@ int mdetr_lsa_forward_fused(const float *logits, const float *boxes, const int64
                             float focal_alpha, int device, void *stream)
 {
     (void)device; (void)stream;
+    if (n <= 0 || n > 128 || kmax < 0 || kmax > 64 || kmax > n) return 1;        // the C ABI's limits (MDETR_E_ARG there)
     const mdetr::MatchWeights mw{w_class, w_bbox, w_center, w_giou, focal_alpha};
     const double INF = 1e300;
     for (int li = 0; li < layers * images; ++li)
@@ -142,8 +143,8 @@ int mdetr_lsa_forward_fused(const float *logits, const float *boxes, const int64
             int32_t *out = assign + (static_cast<int64_t>(li) * groups + g) * kmax;
             for (int t = 0; t < kmax; ++t) out[t] = -1;
             if (k == 0) continue;
-            double a[64][64], u[64] = {0}, v[64] = {0};
-            int p[64];
+            double a[64][128], u[64] = {0}, v[128] = {0};              // kmax <= 64 targets x n <= 128 queries, as the kernel
+            int p[128];
             for (int j = 0; j < n; ++j) {
                 p[j] = -1;
                 const int64_t row = (static_cast<int64_t>(li) * groups + g) * n + j;
@@ -154,9 +155,9 @@ int mdetr_lsa_forward_fused(const float *logits, const float *boxes, const int64
                 }
             }
             for (int i = 0; i < k; ++i) {
-                double minv[64];
-                int way[64];
-                bool used[64];
+                double minv[128];
+                int way[128];
+                bool used[128];
                 for (int j = 0; j < n; ++j) { minv[j] = INF; way[j] = -2; used[j] = false; }
                 int j0 = -1;
                 while (true) {
