@@ -697,6 +697,18 @@ int mdetr_token_wgrad(const void *x, const void *dy, float *partial, int64_t par
                       int device, void *stream);
 
 /*
+ * The same two gradients with x, dy and the partials in fp32 (ABI 14; csrc/twgrad.hip's fp32 form): every operand element is split
+ * once into three bf16 parts (hi, mid, lo) on its way into LDS and a product is six matrix-instruction terms into fp32 accumulators,
+ * db three ones-products -- fp32-accurate (what is dropped is below 2^-24 of |dy||x| per product).  Same partial layout and
+ * chunk-sum contract as mdetr_token_wgrad; deterministic, no atomics.  An infinite operand yields NaN (x - bf16(x)), no fix-up pass.
+ *   x   fp32 [T, C] contiguous, C % 8 == 0;  dy  fp32 [T, N] contiguous, N % 8 == 0;  any T > 0 with T * max(C, N) < 2^29;
+ *   both 16-byte aligned.  MDETR_TUNE="twgrad=0" does not apply: there is no other kernel behind this entry.
+ */
+int mdetr_token_wgrad_f32_chunks(int64_t T, int C, int N);
+int mdetr_token_wgrad_f32(const void *x, const void *dy, float *partial, int64_t partial_floats, int64_t T, int C, int N, int with_bias,
+                          int device, void *stream);
+
+/*
  * y = dropout(relu(x + bias[col] + skip)) over a [rows, cols] channels-last activation in one pass, and its backward --
  * the tails the reference runs as separate operators after a convolution / linear layer: frozen-BN shift + ReLU after the
  * bottleneck's 3x3 convolution and "out += identity; relu(out)" after its expansion (lib/models/monodetr/backbone.py:100-102

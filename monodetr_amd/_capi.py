@@ -75,6 +75,8 @@ SIGNATURES = {
     "mdetr_conv_wgrad": (_c_int, [_c_vp] * 3 + [ctypes.c_int64] + [_c_int] * 9 + [_c_int, _c_vp]),
     "mdetr_token_wgrad_chunks": (_c_int, [ctypes.c_int64, _c_int, _c_int]),
     "mdetr_token_wgrad": (_c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int64, ctypes.c_int64, _c_int, _c_int, _c_int, _c_int, _c_vp]),
+    "mdetr_token_wgrad_f32_chunks": (_c_int, [ctypes.c_int64, _c_int, _c_int]),
+    "mdetr_token_wgrad_f32": (_c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int64, ctypes.c_int64, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     "mdetr_small_wgrad_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, _c_int, _c_int]),
     "mdetr_small_wgrad": (_c_int, [_c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_vp, ctypes.c_int64, ctypes.c_int64, _c_int, _c_int, ctypes.c_int64, ctypes.c_int64, _c_int, _c_vp]),
     "mdetr_group_norm_workspace_bytes": (ctypes.c_int64, [_c_int, ctypes.c_int64, _c_int, _c_int]),

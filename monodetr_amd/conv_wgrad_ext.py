@@ -29,6 +29,10 @@ def supported(x, dy, k, stride):
 # split-K product + chunk sum + two-launch column sum: 53 -> 43 us at [81 600, 256] x [81 600, 256], 49 -> 28-36 us on the backbone's
 # and the depth head's shapes (profiles/r04q_wgradbench.json).
 TOKEN_ROUTE = True
+# MDETR_TWGRAD_F32=1: the same two gradients of FP32 token matrices through the fp32 form of csrc/twgrad.hip (mdetr_token_wgrad_f32:
+# operands split three ways into bf16, six matrix-instruction terms -- fp32-accurate) instead of the library's batched product + chunk
+# sum + column sum.  A family of its own: separate from ENABLED (MDETR_CONV_WGRAD) and from linear._TGEMM_F32.  Opt-in, on no committed list.
+ENABLED_F32 = os.environ.get("MDETR_TWGRAD_F32") == "1"
 
 
 def _chunk_sum_route(chunk_sums, cuda, cols, dtype):
@@ -41,14 +45,18 @@ def _chunk_sum_route(chunk_sums, cuda, cols, dtype):
 
 
 def token_weight_gradient(x2, dy2, dtype, bias=False):
-    """(dW [N, K], db [N] or None) = (dy2^T x2, column sums of dy2) for token matrices x2 [T, K], dy2 [T, N] (bf16, contiguous rows, T a
-    multiple of 8): the 1x1 case of the convolution weight-gradient kernel, the bias gradient riding along on the dy operand that
+    """(dW [N, K], db [N] or None) = (dy2^T x2, column sums of dy2) for token matrices x2 [T, K], dy2 [T, N] (both bf16 or both fp32, contiguous
+    rows): the 1x1 case of the convolution weight-gradient kernel, the bias gradient riding along on the dy operand that
     is already in LDS -- one kernel + one sum over its chunks for both gradients (the library route: a batched split-K product, a
     chunk sum, and a two-launch column sum that reads dy a second time)."""
     T, K = x2.shape
     N = dy2.shape[1]
     lib = _lib()
-    chunks = lib.mdetr_token_wgrad_chunks(T, K, N)
+    if x2.dtype != dy2.dtype or x2.dtype not in (torch.bfloat16, torch.float32):
+        raise RuntimeError("token_wgrad: operands of one dtype, bf16 or fp32 (got %s, %s)" % (x2.dtype, dy2.dtype))
+    # fp32 operands: the fp32 form of the kernel (three-way bf16 split), same partials and chunk sums
+    entry = "mdetr_token_wgrad_f32" if x2.dtype == torch.float32 else "mdetr_token_wgrad"
+    chunks = getattr(lib, entry + "_chunks")(T, K, N)
     if chunks <= 0:
         raise RuntimeError("token_wgrad: unsupported problem")
     cols = N * K + (N if bias else 0)
@@ -60,10 +68,10 @@ def token_weight_gradient(x2, dy2, dtype, bias=False):
         part = W_.get("conv_wgrad", x2.device, chunks * cols * 4).view(torch.float32)[:chunks * cols]
     else:                                            # (a deferred sum reads its partials later: they get a buffer of their own)
         part = torch.empty(chunks * cols, dtype=torch.float32, device=x2.device)
-    rc = lib.mdetr_token_wgrad(x2.data_ptr(), dy2.data_ptr(), part.data_ptr(), part.numel(), T, K, N, 1 if bias else 0,
-                               x2.device.index if cuda else -1, torch.cuda.current_stream(x2.device).cuda_stream if cuda else None)
+    rc = getattr(lib, entry)(x2.data_ptr(), dy2.data_ptr(), part.data_ptr(), part.numel(), T, K, N, 1 if bias else 0,
+                             x2.device.index if cuda else -1, torch.cuda.current_stream(x2.device).cuda_stream if cuda else None)
     if rc != 0:
-        _capi.check(rc, "mdetr_token_wgrad")
+        _capi.check(rc, entry)
     part = part.view(chunks, cols)
     if batched:
         both = chunk_sums.chunk_sum(part, dtype)     # one launch for all the iteration's weight gradients (chunk_sums.flush)
@@ -89,6 +97,16 @@ def token_supported(x2, dy2):
         return ok and T % 8 == 0 and x2.shape[1] % 64 == 0 and dy2.shape[1] % 32 == 0 and dy2.shape[1] >= 128 \
             and ((dy2.shape[1] + 127) // 128) * (x2.shape[1] // 64) <= 64
     return ok and x2.shape[1] % 8 == 0 and dy2.shape[1] % 8 == 0
+
+
+def token_supported_f32(x2, dy2):
+    """fp32 token matrices with contiguous rows whose widths are multiples of 8 (the fp32 form of csrc/twgrad.hip), with the family
+    MDETR_TWGRAD_F32 on -- also under the emulated kernel (tests): the family alone decides, so that fp32 layers keep the library route without it."""
+    T = x2.shape[0]
+    return (TOKEN_ROUTE and ENABLED_F32 and x2.dtype == torch.float32 and dy2.dtype == torch.float32 and x2.dim() == 2
+            and dy2.dim() == 2 and T > 0 and x2.is_contiguous() and dy2.is_contiguous() and (x2.is_cuda or _backend is not None)
+            and x2.data_ptr() % 16 == 0 and dy2.data_ptr() % 16 == 0 and T * max(x2.shape[1], dy2.shape[1]) < (1 << 29)
+            and x2.shape[1] % 8 == 0 and dy2.shape[1] % 8 == 0 and x2.shape[1] > 0 and dy2.shape[1] > 0)
 
 
 def _stolen(like, N, C, k):

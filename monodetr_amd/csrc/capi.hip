@@ -934,6 +934,29 @@ int mdetr_token_wgrad(const void *x, const void *dy, float *partial, int64_t par
     return MDETR_OK;
 }
 
+// The fp32 form of csrc/twgrad.hip (three-way bf16 split, six terms per product).  No twgrad=0 fallback: csrc/conv_wgrad.hip is bf16-only.
+int mdetr_token_wgrad_f32_chunks(int64_t T, int C, int N)
+{
+    if (T <= 0 || C <= 0 || N <= 0 || C % 8 != 0 || N % 8 != 0) return 0;
+    return mdetr::twgrad_f32_chunks(T, C, N);
+}
+
+int mdetr_token_wgrad_f32(const void *x, const void *dy, float *partial, int64_t partial_floats, int64_t T, int C, int N, int with_bias,
+                          int device, void *stream)
+{
+    if (!x || !dy || !partial) return fail(MDETR_E_ARG, "mdetr_token_wgrad_f32: null pointer");
+    if (!mdetr::twgrad_f32_supported(T, C, N, C, N, x, dy))
+        return fail(MDETR_E_ARG, "mdetr_token_wgrad_f32: needs fp32 operands, C %% 8 == 0, N %% 8 == 0, 16-byte aligned operands below 2^31 bytes (T=%lld C=%d N=%d)",
+                    static_cast<long long>(T), C, N);
+    const int64_t need = static_cast<int64_t>(mdetr::twgrad_f32_chunks(T, C, N)) * (static_cast<int64_t>(N) * C + (with_bias ? N : 0));
+    if (partial_floats < need) return fail(MDETR_E_ARG, "mdetr_token_wgrad_f32: partial buffer holds %lld floats, %lld needed", static_cast<long long>(partial_floats), static_cast<long long>(need));
+    DeviceScope dev(device);
+    if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "mdetr_token_wgrad_f32: set device %d: %s", device, hipGetErrorString(dev.err));
+    const hipError_t e = mdetr::twgrad_f32_launch(x, dy, partial, T, C, N, C, N, with_bias != 0, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MDETR_E_HIP, "mdetr_token_wgrad_f32: launch failed: %s", hipGetErrorString(e));
+    return MDETR_OK;
+}
+
 int mdetr_bias_act_forward(int io_dtype, int bias_dtype, const void *x, const void *bias, const void *skip, void *y,
                            int64_t rows, int cols, int relu, float dropout_p, uint64_t seed, const uint64_t *seed_dev,
                            int device, void *stream)

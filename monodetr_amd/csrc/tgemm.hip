@@ -32,6 +32,7 @@
 #include <mdetr_wave.h>
 
 #include "add_ln_math.h"
+#include "mdetr_split.h"
 #include "mdetr_transpose.h"
 #include "msda.h"       // profile scopes
 #include "tgemm.h"
@@ -514,18 +515,7 @@ constexpr size_t tgemm32_lds()
     return slabs > tile ? slabs : tile;
 }
 
-// 4 fp32 values (the 16 bytes of a staged piece, or 4 gathered values) -> their hi / mid / lo bf16 parts, 8 bytes each
-__device__ __forceinline__ void split4(const float (&x)[4], bf16x4 &h, bf16x4 &m, bf16x4 &l)
-{
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const __bf16 hi = static_cast<__bf16>(x[i]);
-        const float r1 = x[i] - static_cast<float>(hi);               // exact
-        const __bf16 mi = static_cast<__bf16>(r1);
-        h[i] = hi; m[i] = mi; l[i] = static_cast<__bf16>(r1 - static_cast<float>(mi));     // exact again; <= 8 significant bits are left
-    }
-}
-
+// (split4: the three-way split of 4 fp32 values, mdetr_split.h -- shared with csrc/twgrad.hip's fp32 form)
 // BK: contraction values per slab;  PF: register sets as in tgemm_kernel;  MASK: the masked tail (NN only)
 template <int BM, int BN, int BK, bool NN, int PF, bool MASK>
 __global__ __launch_bounds__(256, 2)

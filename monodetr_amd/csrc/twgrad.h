@@ -12,4 +12,11 @@ int twgrad_chunks(int64_t T, int C, int N);
 hipError_t twgrad_launch(const void *x, const void *dy, float *part, int64_t T, int C, int N, int64_t ldx, int64_t ldy, bool with_db,
                          hipStream_t st);
 
+// The fp32 form: fp32 x [T, C], dy [T, N] (row strides % 4 == 0), same partial layout; C % 8 == 0, N % 8 == 0; 16-byte aligned;
+// T ld < 2^29 elements (byte offsets fit 32 bits)
+bool twgrad_f32_supported(int64_t T, int C, int N, int64_t ldx, int64_t ldy, const void *x, const void *dy);
+int twgrad_f32_chunks(int64_t T, int C, int N);
+hipError_t twgrad_f32_launch(const void *x, const void *dy, float *part, int64_t T, int C, int N, int64_t ldx, int64_t ldy, bool with_db,
+                             hipStream_t st);
+
 }  // namespace mdetr

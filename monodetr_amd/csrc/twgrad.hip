@@ -19,12 +19,40 @@
 // (deterministic, no atomics).  db rides on the dY fragments already in registers: one more MFMA against a matrix of ones on the
 // waves of the first column tile.
 // Algorithmic bytes = 2 T (N + C) + 4 N C; flops = 2 T N C.
+//
+// The fp32 form (mdetr_token_wgrad_f32; twgrad32_kernel below, a sibling kernel -- the bf16 kernel has no run-time flag for it): X, dY and
+// the partials in fp32, on the SAME matrix instruction.  Operands arrive through buffer-resource loads of 16 bytes (4 fp32; rows >= T and
+// columns >= N / C read zero); each element is split ONCE, on its way from the staging registers into LDS, into hi = bf16(x), mid =
+// bf16(x - hi), lo = bf16(x - hi - mid) (mdetr_split.h, shared with csrc/tgemm.hip), stored as THREE row-major bf16 planes per operand
+// with the bf16 form's row geometry, so tr_fragment reads each plane unchanged.  A k-step issues the six terms lo.hi, hi.lo, mid.mid,
+// mid.hi, hi.mid, hi.hi (dY part x X part, small ones first) into the same fp32 accumulators; db takes three ones-MFMAs (lo, mid, hi
+// of dY) on the waves that carry it in the bf16 form.  Partials have the bf16 form's layout and go through the same chunk sum: no
+// atomics, deterministic.  Non-finite inputs behave as in mdetr_tgemm_f32: x - bf16(x) is NaN for +-inf, so an infinite operand yields
+// NaN (the library yields +-inf); there is no fix-up pass.
+// Choices (the three constraints):
+//   LDS / residency: 2 buffers x 3 planes x TS rows x (BN + BC + 64) bf16.  At the bf16 form's TS = 32 the 128 x 128 tile would need
+//     120 KB -- one four-wave workgroup per CU (160 KB per CU: a request above 80 KB halves residency).  The slab is therefore 16
+//     tokens for 128 x 128 (60 KB) and for 128 x 64 / 64 x 128 (48 KB), 32 for 64 x 64 (72 KB): every instantiation keeps two
+//     workgroups (8 waves) per CU (static_assert in the launcher).  A 16-token slab is one k-step: 24 / 12 MFMAs between two barriers,
+//     12 / 9 fragments (24 / 18 transposing reads) per k-step.  Two wave groups per workgroup (the bf16 form's KG = 2) are NOT built: the
+//     reduction buffer fits, but two groups' slab buffers (120 KB) do not; MDETR_TUNE's twgrad_kg is accepted and has no effect here.
+//   Transposing reads: a plane is TS rows of BN + 32 (BC + 32) bf16 -- the pitch (320 / 192 bytes), the plane size and the buffer size
+//     are multiples of 64 bytes, the dynamic LDS base is 16-byte aligned, a lane's address inside a plane is the bf16 form's (a
+//     multiple of 8 bytes): every ds_read_b64_tr_b16 address is 8-byte aligned.  The 64-byte row pad is kept (4 rows of a read on 4
+//     distinct quarter bank rows, as in the bf16 form -- a plane IS a bf16 slab image).  All branches before the last fragment read
+//     are workgroup- or wave-uniform (chunk >= chunks, the slab loop, want_db): the reads run with EXEC all ones.
+//   Registers: staging is 2 sets x (YCH + XCH) x 4 VGPRs (32 at 128 x 128), accumulators 64 (+ 32 for db), fragments 3 x 4 x 4 = 48;
+//     __launch_bounds__(256, 2) gives the 256-register budget of two waves per SIMD.  No instantiation uses scratch
+//     (scripts/kernel_meta.sh: 180 / 136 / 122 / 102 VGPRs, private segment 0; profiles/r08a_kernel_meta_twgrad.txt).
+// Algorithmic bytes = 4 T (N + C) + 4 N C; flops = 2 T N C (the six terms are an implementation cost).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <mdetr_wave.h>
 
+#include "mdetr_split.h"
 #include "msda.h"       // profile scopes
 #include "twgrad.h"
 #include "mdetr_tune.h"
@@ -288,6 +316,230 @@ hipError_t launch_tile(TwgradArgs g, hipStream_t st)
     return hipGetLastError();
 }
 
+// ================================================================================================================================
+// The fp32 form: see the header comment.  BN x BC: the tile of dW; TS: tokens per slab (a multiple of 16); PF: register sets.
+struct Twgrad32Args {
+    const float *x, *dy;
+    float *part;
+    int64_t T, ldx, ldy, part_stride;
+    int C, N, tiles_n, tiles_c, chunks, slabs, slabs_per_chunk, with_db;
+};
+
+template <int BN, int BC, int TS>
+constexpr size_t twgrad32_lds() { return static_cast<size_t>(2) * 3 * TS * ((BN + kRowPad) + (BC + kRowPad)) * 2; }
+
+template <int BN, int BC, int TS, int PF>
+__global__ __launch_bounds__(kThreadsW, 2)
+void twgrad32_kernel(const Twgrad32Args g)
+{
+    constexpr int PN = BN + kRowPad, PC = BC + kRowPad;          // row pitches of the planes (bf16)
+    constexpr int YP = TS * PN, XP = TS * PC;                    // one plane of a slab image
+    constexpr int TN = BN / 64, TC = BC / 64;                    // 32 x 32 blocks of a wave along n / c
+    constexpr int YCH = TS * BN / 4 / kThreadsW, XCH = TS * BC / 4 / kThreadsW;      // 16-byte pieces (4 fp32) per thread and slab
+    static_assert(YCH >= 1 && XCH >= 1 && TS % 16 == 0, "a slab gives every thread at least one piece of each operand");
+    static_assert((PN * 2) % 8 == 0 && (PC * 2) % 8 == 0 && (YP * 2) % 8 == 0 && (XP * 2) % 8 == 0, "transposing reads: 8-byte aligned rows and planes");
+    MDETR_DYNAMIC_LDS(unsigned char, tw32_smem);
+    __bf16 *Ys = reinterpret_cast<__bf16 *>(tw32_smem);          // [2][3][TS][PN]  (buffer, plane hi / mid / lo)
+    __bf16 *Xs = Ys + 2 * 3 * YP;                                // [2][3][TS][PC]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
+    const int wn = wave & 1, wc = wave >> 1;
+    const int tiles = g.tiles_n * g.tiles_c;
+    const int id = blockIdx.x, grp = id >> 3;
+    const int tile = grp % tiles, chunk = (grp / tiles) * 8 + (id & 7);
+    if (chunk >= g.chunks) return;                               // (workgroup-uniform: the chunk count was rounded up to a multiple of 8)
+    const int n0 = (tile / g.tiles_c) * BN, c0 = (tile % g.tiles_c) * BC;
+    const int s_begin = chunk * g.slabs_per_chunk;
+    const int s_end = s_begin + g.slabs_per_chunk < g.slabs ? s_begin + g.slabs_per_chunk : g.slabs;
+
+    // buffer-resource loads: rows beyond T and columns beyond N / C give zeros (T ld < 2^29 elements: byte offsets fit 32 bits)
+    const mdetr_rsrc yr = make_rsrc(g.dy, static_cast<unsigned>(((g.T - 1) * g.ldy + g.N) * 4));
+    const mdetr_rsrc xr = make_rsrc(g.x, static_cast<unsigned>(((g.T - 1) * g.ldx + g.C) * 4));
+    int yrow[YCH], xrow[XCH], ydst[YCH], xdst[XCH];
+    unsigned ycol[YCH], xcol[XCH];                               // byte offset of the piece inside its row (kRsrcOob: dead column)
+#pragma unroll
+    for (int j = 0; j < YCH; ++j) {
+        const int c = tid + kThreadsW * j, row = c / (BN / 4), pc = c % (BN / 4);
+        yrow[j] = row;
+        ycol[j] = n0 + pc * 4 < g.N ? static_cast<unsigned>((n0 + pc * 4) * 4) : kRsrcOob;      // (N % 8 == 0: a piece of 4 is whole or dead)
+        ydst[j] = row * PN + pc * 4;
+    }
+#pragma unroll
+    for (int j = 0; j < XCH; ++j) {
+        const int c = tid + kThreadsW * j, row = c / (BC / 4), pc = c % (BC / 4);
+        xrow[j] = row;
+        xcol[j] = c0 + pc * 4 < g.C ? static_cast<unsigned>((c0 + pc * 4) * 4) : kRsrcOob;
+        xdst[j] = row * PC + pc * 4;
+    }
+    bf16x8 yst[PF][YCH], xst[PF][XCH];                           // 16 bytes = 4 fp32 each (the load moves bits)
+    auto fetch = [&](int i, bf16x8 (&ys_)[YCH], bf16x8 (&xs_)[XCH]) __attribute__((always_inline)) {
+        const int64_t t0 = static_cast<int64_t>(s_begin + i) * TS;
+#pragma unroll
+        for (int j = 0; j < YCH; ++j) {
+            const int64_t t = t0 + yrow[j];
+            ys_[j] = rsrc_load_bf16x8(yr, (t < g.T && ycol[j] != kRsrcOob) ? static_cast<unsigned>(t * g.ldy * 4) + ycol[j] : kRsrcOob, 0u);
+        }
+#pragma unroll
+        for (int j = 0; j < XCH; ++j) {
+            const int64_t t = t0 + xrow[j];
+            xs_[j] = rsrc_load_bf16x8(xr, (t < g.T && xcol[j] != kRsrcOob) ? static_cast<unsigned>(t * g.ldx * 4) + xcol[j] : kRsrcOob, 0u);
+        }
+    };
+    // the split happens here, once per element: three 8-byte stores, one per plane
+    auto put3 = [&](__bf16 *plane0, int plane, int dst, const bf16x8 &v) __attribute__((always_inline)) {
+        float x[4];
+        __builtin_memcpy(x, &v, 16);
+        bf16x4 h, m, l;
+        split4(x, h, m, l);
+        *reinterpret_cast<bf16x4 *>(plane0 + dst) = h;
+        *reinterpret_cast<bf16x4 *>(plane0 + plane + dst) = m;
+        *reinterpret_cast<bf16x4 *>(plane0 + 2 * plane + dst) = l;
+    };
+    auto deposit = [&](int buf, const bf16x8 (&ys_)[YCH], const bf16x8 (&xs_)[XCH]) __attribute__((always_inline)) {
+        __bf16 *yb = Ys + buf * 3 * YP, *xb = Xs + buf * 3 * XP;
+#pragma unroll
+        for (int j = 0; j < YCH; ++j) put3(yb, YP, ydst[j], ys_[j]);
+#pragma unroll
+        for (int j = 0; j < XCH; ++j) put3(xb, XP, xdst[j], xs_[j]);
+    };
+
+    f32x16 acc[TN][TC], accb[TN];
+#pragma unroll
+    for (int a_ = 0; a_ < TN; ++a_) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) accb[a_][i] = 0.f;
+#pragma unroll
+        for (int b_ = 0; b_ < TC; ++b_)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[a_][b_][i] = 0.f;
+    }
+    const bool want_db = g.with_db != 0 && c0 == 0 && wc == 0;   // (wave-uniform) the first column tile's first column waves carry db
+    bf16x8 ones;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ones[i] = static_cast<__bf16>(1.0f);
+
+    auto products = [&](int buf) __attribute__((always_inline)) {
+        const __bf16 *yb = Ys + buf * 3 * YP + wn * (BN / 2), *xb = Xs + buf * 3 * XP + wc * (BC / 2);
+#pragma unroll
+        for (int ks = 0; ks < TS / 16; ++ks) {
+            bf16x8 yf[3][TN], xf[3][TC];
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+#pragma unroll
+                for (int a_ = 0; a_ < TN; ++a_) yf[p][a_] = tr_fragment(yb + p * YP + ks * 16 * PN + a_ * 32, PN, lane);
+#pragma unroll
+                for (int b_ = 0; b_ < TC; ++b_) xf[p][b_] = tr_fragment(xb + p * XP + ks * 16 * PC + b_ * 32, PC, lane);
+            }
+            // the six terms (dY part x X part), small ones first, term by term over the wave's blocks: lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi
+            constexpr int term_y[6] = {2, 0, 1, 1, 0, 0}, term_x[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+            for (int t = 0; t < 6; ++t)
+#pragma unroll
+                for (int a_ = 0; a_ < TN; ++a_)
+#pragma unroll
+                    for (int b_ = 0; b_ < TC; ++b_) acc[a_][b_] = mfma_bf16(yf[term_y[t]][a_], xf[term_x[t]][b_], acc[a_][b_]);
+            if (want_db) {
+#pragma unroll
+                for (int p = 2; p >= 0; --p)                     // lo, mid, hi of dY against ones
+#pragma unroll
+                    for (int a_ = 0; a_ < TN; ++a_) accb[a_] = mfma_bf16(yf[p][a_], ones, accb[a_]);
+            }
+        }
+    };
+
+    // ---- slab pipeline: the bf16 form's
+    const int ns = s_end - s_begin;
+    if (ns > 0) {
+        fetch(0, yst[PF - 1], xst[PF - 1]);
+#pragma unroll
+        for (int p = 0; p < PF - 1; ++p)
+            if (1 + p < ns) fetch(1 + p, yst[p], xst[p]);
+        deposit(0, yst[PF - 1], xst[PF - 1]);
+        if (PF < ns) fetch(PF, yst[PF - 1], xst[PF - 1]);
+        __syncthreads();
+        for (int k = 0; k < ns; k += PF) {
+#pragma unroll
+            for (int p = 0; p < PF; ++p) {
+                const int s = k + p;
+                if (s < ns) {                                    // (uniform)
+                    if (s + 1 < ns) deposit((s + 1) & 1, yst[p], xst[p]);
+                    if (s + 1 + PF < ns) fetch(s + 1 + PF, yst[p], xst[p]);
+                    products(s & 1);
+                    __syncthreads();
+                }
+            }
+        }
+    }
+
+    // ---- this chunk's partial (the bf16 form's layout)
+    float *pp = g.part + static_cast<int64_t>(chunk) * g.part_stride;
+#pragma unroll
+    for (int a_ = 0; a_ < TN; ++a_) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int n = n0 + wn * (BN / 2) + a_ * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (n >= g.N) continue;
+            if (want_db && l31 == 0) pp[static_cast<int64_t>(g.N) * g.C + n] = accb[a_][r];
+#pragma unroll
+            for (int b_ = 0; b_ < TC; ++b_) {
+                const int c = c0 + wc * (BC / 2) + b_ * 32 + l31;
+                if (c < g.C) pp[static_cast<int64_t>(n) * g.C + c] = acc[a_][b_][r];
+            }
+        }
+    }
+}
+
+struct Twgrad32Plan {
+    int bn, bc, ts, tiles_n, tiles_c, chunks, slabs, slabs_per_chunk;
+};
+
+Twgrad32Plan plan32(int64_t T, int C, int N)
+{
+    Twgrad32Plan p;
+    p.bn = N <= 64 ? 64 : 128;
+    p.bc = C <= 64 ? 64 : 128;
+    char tune_buf[16];
+    if (const char *ev = tune_str("twgrad_f32_tile", tune_buf, sizeof(tune_buf))) {      // tests: "128x64" (BN x BC); any tile takes any problem
+        int n = 0, c = 0;
+        if (sscanf(ev, "%dx%d", &n, &c) == 2 && (n == 64 || n == 128) && (c == 64 || c == 128)) { p.bn = n; p.bc = c; }
+    }
+    p.ts = (p.bn == 64 && p.bc == 64) ? 32 : 16;                 // (LDS: two workgroups per CU, see the header comment)
+    p.tiles_n = (N + p.bn - 1) / p.bn;
+    p.tiles_c = (C + p.bc - 1) / p.bc;
+    p.slabs = static_cast<int>((T + p.ts - 1) / p.ts);
+    // two workgroups per CU, every chunk with at least 128 tokens (the bf16 form's four slabs of 32), chunks in whole eights per XCD
+    int target = 512;
+    { const int f = tune_int("twgrad_wgs", 0); if (f >= 64 && f <= 8192) target = f; }       // tests
+    int chunks = target / (p.tiles_n * p.tiles_c);
+    if (chunks >= 8) chunks = chunks / 8 * 8;
+    const int min_slabs = 128 / p.ts;
+    if (chunks > p.slabs / min_slabs) chunks = p.slabs / min_slabs;
+    if (chunks < 1) chunks = 1;
+    p.slabs_per_chunk = (p.slabs + chunks - 1) / chunks;
+    p.chunks = (p.slabs + p.slabs_per_chunk - 1) / p.slabs_per_chunk;          // every chunk has at least one slab
+    return p;
+}
+
+template <int BN, int BC, int TS>
+hipError_t launch_tile32(Twgrad32Args g, hipStream_t st)
+{
+    constexpr int PF = 2;
+    constexpr size_t lds = twgrad32_lds<BN, BC, TS>();
+    static_assert(lds <= 80 * 1024, "two workgroups per CU");
+    auto kern = twgrad32_kernel<BN, BC, TS, PF>;
+    static bool attr_set[64] = {};
+    int dev_ = 0;
+    if (hipGetDevice(&dev_) != hipSuccess) dev_ = -1;
+    if (dev_ < 0 || dev_ >= 64 || !attr_set[dev_]) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+        if (dev_ >= 0 && dev_ < 64) attr_set[dev_] = true;
+    }
+    const int64_t grid = static_cast<int64_t>((g.chunks + 7) / 8 * 8) * g.tiles_n * g.tiles_c;
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kThreadsW), lds, st, g);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 bool twgrad_supported(int64_t T, int C, int N, int64_t ldx, int64_t ldy, const void *x, const void *dy)
@@ -314,6 +566,32 @@ hipError_t twgrad_launch(const void *x, const void *dy, float *part, int64_t T, 
     if (p.bn == 128) return launch_tile<128, 64, 1>(g, st);
     if (p.bc == 128) return launch_tile<64, 128, 1>(g, st);
     return launch_tile<64, 64, 1>(g, st);
+}
+
+bool twgrad_f32_supported(int64_t T, int C, int N, int64_t ldx, int64_t ldy, const void *x, const void *dy)
+{
+    const auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    return T > 0 && C > 0 && N > 0 && C % 8 == 0 && N % 8 == 0 && ldx % 4 == 0 && ldy % 4 == 0 && ldx >= C && ldy >= N && al(x) && al(dy) &&
+           T * ldx < (1ll << 29) && T * ldy < (1ll << 29) && static_cast<int64_t>(N) * C < (1ll << 28) && T < (1ll << 31) - 64;
+}
+
+int twgrad_f32_chunks(int64_t T, int C, int N) { return plan32(T, C, N).chunks; }
+
+hipError_t twgrad_f32_launch(const void *x, const void *dy, float *part, int64_t T, int C, int N, int64_t ldx, int64_t ldy, bool with_db,
+                             hipStream_t st)
+{
+    const Twgrad32Plan p = plan32(T, C, N);
+    Twgrad32Args g;
+    g.x = static_cast<const float *>(x); g.dy = static_cast<const float *>(dy); g.part = part;
+    g.T = T; g.ldx = ldx; g.ldy = ldy; g.part_stride = static_cast<int64_t>(N) * C + (with_db ? N : 0);
+    g.C = C; g.N = N; g.tiles_n = p.tiles_n; g.tiles_c = p.tiles_c; g.chunks = p.chunks; g.slabs = p.slabs; g.slabs_per_chunk = p.slabs_per_chunk;
+    g.with_db = with_db ? 1 : 0;
+    ProfileScope prof(11, conv_mflop(T, static_cast<int64_t>(C) * N), st, 2.0 * T * N * C / 1e6,
+                      (4.0 * T * (N + C) + 4.0 * p.chunks * (static_cast<double>(N) * C + (with_db ? N : 0))) / 1e3);       // (+ the fp32 partials it writes)
+    if (p.bn == 128 && p.bc == 128) return launch_tile32<128, 128, 16>(g, st);
+    if (p.bn == 128) return launch_tile32<128, 64, 16>(g, st);
+    if (p.bc == 128) return launch_tile32<64, 128, 16>(g, st);
+    return launch_tile32<64, 64, 32>(g, st);
 }
 
 }  // namespace mdetr

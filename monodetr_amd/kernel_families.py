@@ -13,7 +13,7 @@ import os
 AUTOTUNE_SWITCHES = ("MDETR_FUSED_LOSSES", "MDETR_FUSED_ADAMW", "MDETR_MSDA_PROLOGUE", "MDETR_FUSED_LN", "MDETR_MSDA_BF16",
                      "MDETR_FUSED_EPILOGUE", "MDETR_GEMM_RELU", "MDETR_CONV3X3", "MDETR_GROUP_NORM", "MDETR_SMALL_WGRAD",
                      "MDETR_CONV_STRIDED", "MDETR_CONV_WGRAD", "MDETR_CONV_STEM", "MDETR_TGEMM", "MDETR_WFOLD", "MDETR_RELU_PREMASK",
-                     "MDETR_HEADS", "MDETR_CHUNK_SUMS", "MDETR_HEAD_TAIL", "MDETR_TGEMM_F32")
+                     "MDETR_HEADS", "MDETR_CHUNK_SUMS", "MDETR_HEAD_TAIL", "MDETR_TGEMM_F32", "MDETR_TWGRAD_F32")
 ALL_SWITCHES = AUTOTUNE_SWITCHES
 # The measured configuration.  family -> the GPU tests that hold it to the default path / the framework operators
 # (all in tests/test_fused_gpu.py unless a file is named); a family without green tests is not listed.
@@ -33,6 +33,7 @@ SWITCH_TESTS = {
     "MDETR_TGEMM": "test_tgemm_gpu.py::test_tgemm_*, test_training_step_with_the_token_gemm_kernel_*, test_bottleneck_with_fused_tails_*, test_exact_products_gpu.py::test_exact_tgemm_bf16_*, test_exact_products_gpu.py::test_exact_decimate_and_pointwise_conv",
     "MDETR_WFOLD": "test_fold_kernel_*, test_training_step_with_the_fold_kernel_*",
     "MDETR_TGEMM_F32": "test_tgemm_f32_gpu.py::test_tgemm_f32_*, test_tgemm_f32_gpu.py::test_fp32_modules_with_the_switch_*, test_exact_products_gpu.py::test_exact_tgemm_f32_*",
+    "MDETR_TWGRAD_F32": "test_twgrad_f32_gpu.py::test_twgrad_f32_*, test_twgrad_f32_gpu.py::test_fp32_stage_with_both_switches_*",
     "MDETR_RELU_PREMASK": "test_tgemm_gpu.py::test_masked_input_gradient_*, test_tgemm_gpu.py::test_bottleneck_stage_with_premasked_relu_*, test_exact_products_gpu.py::test_exact_tgemm_masked_*",
     "MDETR_HEADS": "test_sgemm_gpu.py::test_sgemm_*, test_sgemm_gpu.py::test_heads_level_*, test_training_step_with_the_grouped_heads_*, test_exact_products_gpu.py::test_exact_sgemm_grouped_*",
     "MDETR_HEAD_TAIL": "test_sgemm_gpu.py::test_head_tail_*, test_sgemm_gpu.py::test_training_step_with_the_head_tail_*",
@@ -56,6 +57,8 @@ COMMITTED_SWITCHES = {
     # one call, bit-identical gradients (profiles/r05z2_step_ab_premask.log).
     # MDETR_TGEMM_F32: the fp32 form of the same products (mdetr_tgemm_f32: three-way bf16 split, six MFMA terms).  Opt-in: on NO
     # committed list; whether it joins "fp32" is decided on the step A/B recorded in DESIGN.md 3.3.
+    # MDETR_TWGRAD_F32: the weight / bias gradients of the same fp32 layers through the fp32 form of csrc/twgrad.hip
+    # (mdetr_token_wgrad_f32).  Opt-in: on NO committed list; DESIGN.md 3.4 records the per-shape and step figures.
     "bf16": ("MDETR_FUSED_LOSSES", "MDETR_FUSED_ADAMW", "MDETR_FUSED_LN", "MDETR_MSDA_PROLOGUE", "MDETR_MSDA_BF16",
              "MDETR_FUSED_EPILOGUE", "MDETR_GEMM_RELU", "MDETR_CONV3X3", "MDETR_GROUP_NORM", "MDETR_SMALL_WGRAD",
              "MDETR_CONV_WGRAD", "MDETR_CONV_STRIDED", "MDETR_CONV_STEM", "MDETR_TGEMM", "MDETR_WFOLD", "MDETR_RELU_PREMASK", "MDETR_HEADS",
@@ -101,6 +104,7 @@ def apply_switches(names):
     conv3x3_ext.ENABLED = "MDETR_CONV3X3" in names
     conv_taps_ext.ENABLED = "MDETR_CONV_STRIDED" in names
     conv_wgrad_ext.ENABLED = "MDETR_CONV_WGRAD" in names
+    conv_wgrad_ext.ENABLED_F32 = "MDETR_TWGRAD_F32" in names
     conv_stem_ext.ENABLED = "MDETR_CONV_STEM" in names
     group_norm_ext.ENABLED = "MDETR_GROUP_NORM" in names
     small_wgrad_ext.ENABLED = "MDETR_SMALL_WGRAD" in names

@@ -4,8 +4,9 @@ channels-last maps) with its autograd structure, and the router that decides whi
 bf16 operands on the GPU with MDETR_TGEMM (the committed bf16 list): forward and input gradient through csrc/tgemm.hip -- bias,
 ReLU, Dropout, "+ identity" and the residual-path gradient in the product's epilogue -- and the weight + bias gradient through
 csrc/twgrad.hip (>= 1 024 rows) or csrc/small_wgrad.hip, chunk partials summed by csrc/colsum.hip.  fp32 operands with
-MDETR_TGEMM_F32 (opt-in): forward and input gradient through the fp32 form of csrc/tgemm.hip, same epilogues; their weight gradients
-keep the library route.  Everything else (fp32 without that switch, autocast,
+MDETR_TGEMM_F32 (opt-in): forward and input gradient through the fp32 form of csrc/tgemm.hip, same epilogues; with
+MDETR_TWGRAD_F32 (opt-in, a switch of its own): the weight + bias gradient of fp32 layers above small_wgrad's rows through the fp32
+form of csrc/twgrad.hip -- one launch + one chunk sum for both.  Everything else (fp32 without those switches, mixed dtypes, autocast,
 CPU tensors, operands the kernels' alignment rules refuse) takes the library GEMMs with the SAME autograd functions: a batched
 split-K product for tall weight gradients (the library's single NT GEMM runs 16 workgroups deep at [81 600, 256]^T x [81 600, 256]:
 205 us against 35), `colsum` for the bias.  Rules, not probing: nothing is timed at run time.
@@ -33,6 +34,15 @@ _TGEMM_F32 = os.environ.get("MDETR_TGEMM_F32") == "1"
 # rows from which a bf16 weight gradient takes csrc/twgrad.hip instead of csrc/small_wgrad.hip: the decoder's 4 400 and layer4's 3 840
 # rows included (421.7 -> 426.9 img/s, profiles/r05n_step_ab_twgrad_small_rows.log)
 _TWGRAD_MIN_ROWS = 1024
+
+
+# rows from which an FP32 weight gradient takes the fp32 form of csrc/twgrad.hip (MDETR_TWGRAD_F32) instead of csrc/small_wgrad.hip:
+# everything above small_wgrad's MAX_ROWS, where the kernel + chunk sum beat today's route at every step shape (85 vs 114 us at
+# [81 600, 256] x [81 600, 256], 68 vs 98 at layer3's 256 -> 1024; 1 028 vs 1 362 us over the 12 shapes, spread <= 8 us).  The class
+# [_TWGRAD_MIN_ROWS, MAX_ROWS] stays: of its seven shapes four are faster (decoder FFN 35.7 vs 48.2 us, proj2 42 vs 76) but the
+# decoder's 256 -> 256 products, its most frequent shape, are slower (22.3 vs 19.1 us on small_wgrad, spread 0.2) and layer4's
+# projection shortcut much slower (201 vs 129): rows cannot tell them apart (profiles/r08a_wgradbench_fp32.json).
+_TWGRAD_F32_MIN_ROWS = small_wgrad_ext.MAX_ROWS + 1
 
 
 # MDETR_RELU_PREMASK=1: the ReLU backward between two kernels of this repository is applied where the CONSUMER's input gradient leaves
@@ -140,6 +150,15 @@ def _split_count(T):
     return best
 
 
+def _token_kernel_ok(x2, dy2, dt):
+    """Does csrc/twgrad.hip take these operands?  bf16: family MDETR_CONV_WGRAD; fp32 operands with an fp32 result from
+    `_TWGRAD_F32_MIN_ROWS` rows on: family MDETR_TWGRAD_F32.  Mixed dtypes: never."""
+    from .. import conv_wgrad_ext
+    if conv_wgrad_ext.token_supported(x2, dy2):
+        return True
+    return dt == torch.float32 and x2.shape[0] >= _TWGRAD_F32_MIN_ROWS and conv_wgrad_ext.token_supported_f32(x2, dy2)
+
+
 def _weight_bias_grads(x2, dy2, weight, need_w, need_b, bias_dtype=None, out_dtype=None):
     """(dW, db) of y = x W^T + b from the [T, K] input and the [T, N] output gradient (either may be None when not needed), in the
     weight's dtype (or `out_dtype`).  bias_dtype: the bias parameter's dtype where it differs from the weight's -- an fp32 bias
@@ -155,7 +174,7 @@ def _weight_bias_grads(x2, dy2, weight, need_w, need_b, bias_dtype=None, out_dty
     if need_w and _TWGRAD_MIN_ROWS <= T <= small_wgrad_ext.MAX_ROWS and dt in (torch.float32, torch.bfloat16):
         # a few thousand rows of bf16 operands (the decoder's 4 400, layer4's 3 840): csrc/twgrad.hip as well (_TWGRAD_MIN_ROWS)
         from .. import conv_wgrad_ext
-        if conv_wgrad_ext.token_supported(x2, dy2):
+        if _token_kernel_ok(x2, dy2, dt):
             return conv_wgrad_ext.token_weight_gradient(x2, dy2, dt, bias=need_b)
     if small_wgrad_ext.ENABLED and need_w and (T <= small_wgrad_ext.MAX_ROWS or dy2.shape[1] <= 64) \
             and dt in (torch.float32, torch.bfloat16) and small_wgrad_ext.supported(dy2, x2):
@@ -167,8 +186,8 @@ def _weight_bias_grads(x2, dy2, weight, need_w, need_b, bias_dtype=None, out_dty
     C = _split_count(T) if T > small_wgrad_ext.MAX_ROWS else 0
     if need_w:
         from .. import conv_wgrad_ext
-        if T > small_wgrad_ext.MAX_ROWS and conv_wgrad_ext.token_supported(x2, dy2) and dt in (torch.float32, torch.bfloat16):
-            # dW and db from ONE kernel + one chunk sum (csrc/twgrad.hip, the bias gradient riding along)
+        if T > small_wgrad_ext.MAX_ROWS and dt in (torch.float32, torch.bfloat16) and _token_kernel_ok(x2, dy2, dt):
+            # dW and db from ONE kernel + one chunk sum (csrc/twgrad.hip, bf16 or fp32 form, the bias gradient riding along)
             return conv_wgrad_ext.token_weight_gradient(x2, dy2, dt, bias=need_b)
         elif C:
             parts = torch.bmm(dy2.view(C, T // C, -1).transpose(1, 2), x2.view(C, T // C, -1))    # [C, N, K]
