@@ -37,11 +37,17 @@ MDETR_HD void pro_softmax(const float *logit, int LP, float *attn)
     for (int i = 0; i < LP; ++i) attn[i] *= inv;
 }
 
-// g_logit = attn * (g_attn - sum_i attn_i g_attn_i)
+// g_logit = attn * (g_attn - sum_i attn_i g_attn_i).  The sum is a chain of explicit fused multiply-adds with contraction off: left to
+// the compiler, the unrolled LP = 16 kernels fused some terms and paired others (v_pk_mul_f32 + adds) differently in every
+// instantiation, and on a peaked row, where g_attn - dot cancels, the last bit of dot is the 10th bit of that row's largest gradient --
+// the bf16-I/O kernels then rounded a different fp32 number than the fp32-I/O kernels computed.
 MDETR_HD void pro_softmax_backward(const float *attn, const float *g_attn, int LP, float *g_logit)
 {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
     float dot = 0.f;
-    for (int i = 0; i < LP; ++i) dot += attn[i] * g_attn[i];
+    for (int i = 0; i < LP; ++i) dot = fmaf(attn[i], g_attn[i], dot);
     for (int i = 0; i < LP; ++i) g_logit[i] = attn[i] * (g_attn[i] - dot);
 }
 

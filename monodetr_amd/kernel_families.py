@@ -21,7 +21,7 @@ SWITCH_TESTS = {
     "MDETR_FUSED_LOSSES": "test_fused_pair_losses_*, test_fused_ddn_loss_*, test_fused_cost_solver_*, test_training_step_with_fused_criterion_*",
     "MDETR_FUSED_ADAMW": "test_fused_adamw_kernel_*, test_fused_adamw_vs_recorded_reference_steps, test_training_step_with_fused_adamw_*",
     "MDETR_FUSED_LN": "test_fused_add_layernorm_*, test_training_step_with_fused_layernorm_*, test_chunk_sums_tall_gpu.py::test_fused_add_layernorm_*",
-    "MDETR_MSDA_PROLOGUE": "test_msda_prologue_kernel_*",
+    "MDETR_MSDA_PROLOGUE": "test_msda_prologue_kernel_*, test_prologue_cases_gpu.py::test_msda_prologue_kernel_*",
     "MDETR_MSDA_BF16": "test_msda_bf16_kernels_*, test_msda_function_with_native_bf16_*, test_training_step_with_bf16_msda_*, test_msda_gpu.py::test_bf16_native_full_encoder_shape_vs_oracle",
     "MDETR_FUSED_EPILOGUE": "test_bias_act_kernel_*, test_training_step_with_fused_tails_*",
     "MDETR_GEMM_RELU": "test_library_gemm_relu_epilogue_*, test_training_step_with_fused_tails_*",
@@ -36,7 +36,7 @@ SWITCH_TESTS = {
     "MDETR_TWGRAD_F32": "test_twgrad_f32_gpu.py::test_twgrad_f32_*, test_twgrad_f32_gpu.py::test_fp32_stage_with_both_switches_*",
     "MDETR_RELU_PREMASK": "test_tgemm_gpu.py::test_masked_input_gradient_*, test_tgemm_gpu.py::test_bottleneck_stage_with_premasked_relu_*, test_exact_products_gpu.py::test_exact_tgemm_masked_*",
     "MDETR_HEADS": "test_sgemm_gpu.py::test_sgemm_*, test_sgemm_gpu.py::test_heads_level_*, test_training_step_with_the_grouped_heads_*, test_exact_products_gpu.py::test_exact_sgemm_grouped_*",
-    "MDETR_HEAD_TAIL": "test_sgemm_gpu.py::test_head_tail_*, test_sgemm_gpu.py::test_training_step_with_the_head_tail_*",
+    "MDETR_HEAD_TAIL": "test_sgemm_gpu.py::test_head_tail_*, test_sgemm_gpu.py::test_training_step_with_the_head_tail_*, test_head_tail_cases_gpu.py::test_head_tail_*",
     "MDETR_CHUNK_SUMS": "test_colsum_gpu.py::test_chunk_sums_*, test_colsum_gpu.py::test_deferred_chunk_sums_*, test_chunk_sums_tall_gpu.py::test_chunk_sums_*",
     "MDETR_CONV3X3": "test_conv3x3_kernel_matches_the_library_convolution, test_training_step_with_the_conv3x3_kernel_*, test_conv3x3_module_with_a_trainable_bias_*, test_exact_products_gpu.py::test_exact_conv3x3_*",
 }
