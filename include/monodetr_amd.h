@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MDETR_ABI_VERSION 14
+#define MDETR_ABI_VERSION 15
 
 /* element types of the floating-point tensors */
 #define MDETR_F32 0
@@ -625,6 +625,19 @@ int mdetr_conv3x3_plan(int B, int H, int W, int N);
  * self.relu(out)` between conv1 and conv2) applied where the gradient leaves the chip: mask = conv2's input. */
 int mdetr_conv3x3_masked(const void *x, const void *w, const float *shift, const void *mask, void *y, int B, int H, int W, int C, int N,
                          int relu, int device, void *stream);
+/* The fp32 form (csrc/conv3x3.hip, conv3x3_f32_kernel): x, w, shift, mask and y are fp32.  Each operand is split once into three
+ * bf16 parts (hi, mid, lo) on its way into LDS and a product is six matrix-instruction terms, small ones first, into one fp32
+ * accumulator -- fp32-accurate (what is dropped is below 2^-24 of |x||w| per product); shift, ReLU and mask are applied in fp32
+ * and y is written without any further rounding.  Deterministic, no atomics.  An infinite operand yields NaN (x - bf16(x)).
+ *   x      fp32 [B, H, W, C], C % 64 == 0, 16-byte aligned;  w  fp32 [N, 3, 3, C], N % 32 == 0, 16-byte aligned
+ *   shift  fp32 [N] or NULL;  mask  fp32 [B, H, W, N], 16-byte aligned, or NULL: y is zeroed where mask <= 0
+ *   y      fp32 [B, H, W, N], 16-byte aligned;  flags: those of mdetr_conv3x3_masked's `relu` (bit 0 ReLU, bit 1 mirrored taps)
+ *   H W C < 2^29 and 9 N C < 2^29 (32-bit byte offsets of one image / the weight).  B == 0 returns 0 without a launch.
+ * MDETR_TUNE keys conv3x3_f32_tile (10 WC + GC) and conv3x3_f32_nb (1 or 2) force the geometry; the bf16 keys do not apply. */
+int mdetr_conv3x3_f32(const void *x, const void *w, const float *shift, const void *mask, void *y, int B, int H, int W, int C, int N,
+                      int flags, int device, void *stream);
+/* The launch geometry mdetr_conv3x3_f32 takes for a shape (host only): 100 x WC + 10 x GC + NB as mdetr_conv3x3_plan, NB in {1, 2}. */
+int mdetr_conv3x3_f32_plan(int B, int H, int W, int N);
 
 /*
  * The strided convolutions of the ResNet body, the fourth pyramid level and the depth predictor, and their input gradients, as

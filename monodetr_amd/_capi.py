@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MDETR_LIB_PATH") or os.path.join(_HERE, "libmonodetr_
 
 MDETR_F32, MDETR_F64, MDETR_BF16 = 0, 1, 2
 MDETR_E_UNSUPPORTED = -4
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _c_int, _c_vp = ctypes.c_int, ctypes.c_void_p
 
@@ -67,6 +67,8 @@ SIGNATURES = {
     "mdetr_conv3x3_forward": (_c_int, [_c_vp] * 4 + [_c_int] * 6 + [_c_int, _c_vp]),
     "mdetr_conv3x3_plan": (_c_int, [_c_int] * 4),
     "mdetr_conv3x3_masked": (_c_int, [_c_vp] * 5 + [_c_int] * 6 + [_c_int, _c_vp]),
+    "mdetr_conv3x3_f32": (_c_int, [_c_vp] * 5 + [_c_int] * 6 + [_c_int, _c_vp]),
+    "mdetr_conv3x3_f32_plan": (_c_int, [_c_int] * 4),
     "mdetr_conv_taps": (_c_int, [_c_vp] * 5 + [_c_int, _c_int, _c_vp]),
     "mdetr_conv_taps_split": (_c_int, [_c_vp] * 4 + [ctypes.c_int64, _c_vp, _c_int, _c_int, _c_vp]),
     "mdetr_conv_dgrad_s2": (_c_int, [_c_vp] * 3 + [_c_int] * 8 + [_c_int, _c_vp]),

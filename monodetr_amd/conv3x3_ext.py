@@ -1,6 +1,7 @@
 """``conv3x3(x, weight, shift, relu)``: 3x3 / stride 1 / pad 1 convolution of a channels_last bf16 activation with the folded
 frozen-BN shift and the ReLU in its epilogue (csrc/conv3x3.hip through ``mdetr_conv3x3_forward``): forward and input gradient
-run on the kernel, the weight gradient on csrc/conv_wgrad.hip (conv_wgrad_ext)."""
+run on the kernel, the weight gradient on csrc/conv_wgrad.hip (conv_wgrad_ext).  With MDETR_CONV3X3_F32=1 fp32 channels_last tensors
+take the fp32 form of the kernel (``mdetr_conv3x3_f32``) for forward and input gradient; their weight gradient stays on the library."""
 import os
 
 import torch
@@ -10,19 +11,41 @@ from . import _capi
 _backend = None               # tests substitute the CPU emulation of the same kernel source (tests/native_emul.py)
 # MDETR_CONV3X3=1 routes the backbone's stride-1 3x3 convolutions through the kernel; on the committed bf16 list of kernel_families.py
 ENABLED = os.environ.get("MDETR_CONV3X3") == "1"
+# MDETR_CONV3X3_F32=1: FP32 channels_last activations take the fp32 form of the same kernel (mdetr_conv3x3_f32: operands split three
+# ways into bf16, six matrix-instruction terms -- fp32-accurate), forward and input gradient; the weight gradient stays on the library
+# (csrc/conv_wgrad.hip is bf16-only).  A family of its own, opt-in, on no committed list.
+ENABLED_F32 = os.environ.get("MDETR_CONV3X3_F32") == "1"
 
 
 def _lib():
     return _backend if _backend is not None else _capi.lib()
 
 
-def supported(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1):
-    """x [B, C, H, W] channels_last bf16, weight [N, C, 3, 3] bf16; stride 1, padding 1, no dilation / groups."""
-    return ((x.is_cuda or _backend is not None) and x.dim() == 4 and weight.dim() == 4 and x.dtype == torch.bfloat16
-            and weight.dtype == torch.bfloat16 and tuple(weight.shape[2:]) == (3, 3) and tuple(stride) == (1, 1)
+def _supported(x, weight, stride, padding, dilation, groups, dtype):
+    return ((x.is_cuda or _backend is not None) and x.dim() == 4 and weight.dim() == 4 and x.dtype == dtype
+            and weight.dtype == dtype and tuple(weight.shape[2:]) == (3, 3) and tuple(stride) == (1, 1)
             and tuple(padding) == (1, 1) and tuple(dilation) == (1, 1) and groups == 1 and weight.shape[1] == x.shape[1]
             and x.shape[1] % 64 == 0 and weight.shape[0] % 32 == 0 and x.numel() > 0
             and x.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0)
+
+
+def supported(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1):
+    """x [B, C, H, W] channels_last bf16, weight [N, C, 3, 3] bf16; stride 1, padding 1, no dilation / groups."""
+    return _supported(x, weight, stride, padding, dilation, groups, torch.bfloat16)
+
+
+def supported_f32(x, weight, stride=(1, 1), padding=(1, 1), dilation=(1, 1), groups=1):
+    """The same for fp32 tensors, with the family MDETR_CONV3X3_F32 on (the family alone decides, also under the emulated kernel)."""
+    return ENABLED_F32 and _supported(x, weight, stride, padding, dilation, groups, torch.float32) \
+        and x.shape[2] * x.shape[3] * x.shape[1] < (1 << 29) and weight.numel() < (1 << 29)
+
+
+def _autocast(x):
+    """Is autocast on for x's device type?  (The fp32 route must not take tensors the library would compute in a lower precision.)"""
+    try:
+        return torch.is_autocast_enabled(x.device.type)
+    except TypeError:                                                  # (a torch whose query takes no device type)
+        return torch.is_autocast_enabled()
 
 
 def _ohwi(weight):
@@ -33,15 +56,25 @@ def _ohwi(weight):
 
 def _launch(x_cl, w_ohwi, shift, relu, mirror=False, mask=None):
     """x_cl [B, C, H, W] channels_last, w_ohwi [N, 3, 3, C] contiguous -> y [B, N, H, W] channels_last.
-    mask [B, N, H, W] channels_last bf16: the result is zeroed where mask <= 0 (``mdetr_conv3x3_masked``)."""
+    mask [B, N, H, W] channels_last, x's dtype: the result is zeroed where mask <= 0 (``mdetr_conv3x3_masked``).
+    fp32 tensors take ``mdetr_conv3x3_f32`` (mask or not); y has x's dtype."""
     B, C, H, W = x_cl.shape
     N = w_ohwi.shape[0]
-    y = torch.empty((B, N, H, W), dtype=torch.bfloat16, device=x_cl.device, memory_format=torch.channels_last)
+    f32 = x_cl.dtype == torch.float32
+    assert w_ohwi.dtype == x_cl.dtype
+    y = torch.empty((B, N, H, W), dtype=x_cl.dtype, device=x_cl.device, memory_format=torch.channels_last)
     cuda = x_cl.is_cuda
     flags = (1 if relu else 0) | (2 if mirror else 0)
     dev_i, stream = x_cl.device.index if cuda else -1, torch.cuda.current_stream(x_cl.device).cuda_stream if cuda else None
     if mask is not None:
-        assert mask.shape == y.shape and mask.dtype == torch.bfloat16 and mask.is_contiguous(memory_format=torch.channels_last)
+        assert mask.shape == y.shape and mask.dtype == x_cl.dtype and mask.is_contiguous(memory_format=torch.channels_last)
+    if f32:
+        rc = _lib().mdetr_conv3x3_f32(x_cl.data_ptr(), w_ohwi.data_ptr(), shift.data_ptr() if shift is not None else None,
+                                      mask.data_ptr() if mask is not None else None, y.data_ptr(), B, H, W, C, N, flags, dev_i, stream)
+        if rc != 0:
+            _capi.check(rc, "mdetr_conv3x3_f32")
+        return y
+    if mask is not None:
         rc = _lib().mdetr_conv3x3_masked(x_cl.data_ptr(), w_ohwi.data_ptr(), shift.data_ptr() if shift is not None else None, mask.data_ptr(),
                                          y.data_ptr(), B, H, W, C, N, flags, dev_i, stream)
     else:
@@ -50,6 +83,15 @@ def _launch(x_cl, w_ohwi, shift, relu, mirror=False, mask=None):
     if rc != 0:
         _capi.check(rc, "mdetr_conv3x3_masked" if mask is not None else "mdetr_conv3x3_forward")
     return y
+
+
+# No fp32 shape class is routed back to the library: tools/convbench --dtype fp32 (profiles/r09a_convbench_fp32.json) has the kernel
+# ahead of the library by more than the library's own spread on all four ResNet stage shapes, forward (109 - 157 us against 176 - 219)
+# and input gradient (108 - 157 against 173 - 184); layer4 is the closest (157 us against 166 - 182).
+def _dx_f32(dy, w):
+    """fp32 input gradient on the kernel: an fp32 weight and the entry's 32-bit offset limits."""
+    B, N, H, W = dy.shape
+    return w.dtype == torch.float32 and H * W * N < (1 << 29) and w.numel() < (1 << 29)
 
 
 class _Conv3x3(torch.autograd.Function):
@@ -85,11 +127,11 @@ class _Conv3x3(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             # dX = conv(dY, w') with w'[c, t, s, n] = w[n, 2 - t, 2 - s, c]: the same kernel on the weight with its channel axes
             # swapped (one small copy), the taps mirrored by the kernel's addressing
-            if dy.shape[1] % 64 == 0 and x.shape[1] % 32 == 0 and dy.data_ptr() % 16 == 0:
+            if dy.shape[1] % 64 == 0 and x.shape[1] % 32 == 0 and dy.data_ptr() % 16 == 0 and (dy.dtype != torch.float32 or _dx_f32(dy, w)):
                 wt = ctx.w_ihwo
                 if wt is None or wt.shape != (w.shape[3], 3, 3, w.shape[0]) or not wt.is_contiguous() or wt.dtype != w.dtype:
                     wt = w.permute(3, 1, 2, 0).contiguous()
-                masked = ctx.in_token is not None and x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last)
+                masked = ctx.in_token is not None and (x.dtype == torch.bfloat16 or x.dtype == dy.dtype) and x.is_contiguous(memory_format=torch.channels_last)
                 dx = _launch(dy, wt, None, False, mirror=True, mask=x if masked else None)
                 if ctx.in_token is not None and not masked:
                     dx = torch.ops.aten.threshold_backward(dx, x, 0.0)
@@ -119,7 +161,7 @@ class _Conv3x3(torch.autograd.Function):
 
 def conv3x3(x, weight, shift=None, relu=False, hand_out_token=False, in_token=None):
     """act(conv2d(x, weight, padding=1) + shift[None, :, None, None]); ``shift`` [N]: a frozen-BN shift or a trainable bias."""
-    if not supported(x, weight):
+    if not supported(x, weight) and not supported_f32(x, weight):
         raise RuntimeError("conv3x3: needs a CUDA bf16 channels_last activation with C % 64 == 0 and a bf16 [N, C, 3, 3] weight with N % 32 == 0")
     return _Conv3x3.apply(x, weight, shift, relu, hand_out_token, in_token if x.requires_grad else None)
 
@@ -129,7 +171,8 @@ class Conv3x3(torch.nn.Conv2d):
     qualifies (3x3 / stride 1 / pad 1, bf16 channels_last, C % 64 == 0, N % 32 == 0), and nn.Conv2d's otherwise."""
 
     def forward(self, x):
-        if ENABLED and x.dtype == self.weight.dtype and not torch.is_autocast_enabled() \
-                and supported(x, self.weight, self.stride, self.padding, self.dilation, self.groups) and self.padding_mode == "zeros":
+        if x.dtype == self.weight.dtype and not torch.is_autocast_enabled() and self.padding_mode == "zeros" \
+                and ((ENABLED and supported(x, self.weight, self.stride, self.padding, self.dilation, self.groups))
+                     or (not _autocast(x) and supported_f32(x, self.weight, self.stride, self.padding, self.dilation, self.groups))):
             return conv3x3(x, self.weight, self.bias, relu=False)
         return super().forward(x)

@@ -770,6 +770,28 @@ int mdetr_conv3x3_masked(const void *x, const void *w, const float *shift, const
     return conv3x3_any("mdetr_conv3x3_masked", x, w, shift, mask, y, B, H, W, C, N, relu, device, stream);
 }
 
+int mdetr_conv3x3_f32_plan(int B, int H, int W, int N)
+{
+    if (B <= 0 || H <= 0 || W <= 0 || N <= 0) return fail(MDETR_E_ARG, "mdetr_conv3x3_f32_plan: bad sizes");
+    return mdetr::conv3x3_f32_plan(B, H, W, N);
+}
+
+int mdetr_conv3x3_f32(const void *x, const void *w, const float *shift, const void *mask, void *y, int B, int H, int W, int C, int N,
+                      int flags, int device, void *stream)
+{
+    const char *who = "mdetr_conv3x3_f32";
+    if (B < 0 || H < 0 || W < 0 || C <= 0 || N <= 0) return fail(MDETR_E_ARG, "%s: bad sizes B=%d H=%d W=%d C=%d N=%d", who, B, H, W, C, N);
+    if (B == 0 || H == 0 || W == 0) return MDETR_OK;
+    if (!x || !w || !y) return fail(MDETR_E_ARG, "%s: null pointer", who);
+    if (!mdetr::conv3x3_f32_supported(B, H, W, C, N, x, w, y, mask))
+        return fail(MDETR_E_ARG, "%s: needs fp32 operands, C %% 64 == 0, N %% 32 == 0, 16-byte aligned x / w / y / mask, H W C and 9 N C below 2^29 (C=%d N=%d)", who, C, N);
+    DeviceScope dev(device);
+    if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "%s: set device %d: %s", who, device, hipGetErrorString(dev.err));
+    const hipError_t e = mdetr::conv3x3_f32_launch(x, w, shift, y, B, H, W, C, N, (flags & 1) != 0, static_cast<hipStream_t>(stream), (flags & 2) != 0, mask);
+    if (e != hipSuccess) return fail(MDETR_E_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+    return MDETR_OK;
+}
+
 int mdetr_conv_taps(const void *x, const void *w, const float *shift, void *y, const int64_t *dims, int relu, int device, void *stream)
 {
     if (!dims) return fail(MDETR_E_ARG, "mdetr_conv_taps: null dims");

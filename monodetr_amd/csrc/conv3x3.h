@@ -15,4 +15,11 @@ hipError_t conv3x3_launch(const void *x, const void *w, const float *shift, void
 // the launcher's choice for a shape: 100 x (columns of a wave's pixel block) + 10 x (blocks side by side) + output-channel blocks of 32
 int conv3x3_plan(int B, int H, int W, int N);
 
+// The fp32 form (conv3x3_f32_kernel): x, w, shift, mask and y fp32, same shapes and flags; x / w / y / mask 16-byte aligned.  Operands
+// are split into three bf16 parts on their way into LDS (mdetr_split.h): an infinite operand yields NaN.
+bool conv3x3_f32_supported(int B, int H, int W, int C, int N, const void *x, const void *w, const void *y, const void *mask);
+hipError_t conv3x3_f32_launch(const void *x, const void *w, const float *shift, void *y, int B, int H, int W, int C, int N, bool relu,
+                              hipStream_t st, bool mirror = false, const void *mask = nullptr);
+int conv3x3_f32_plan(int B, int H, int W, int N);       // as conv3x3_plan, with the fp32 kernel's residency; NB in {1, 2}
+
 }  // namespace mdetr

@@ -236,6 +236,10 @@ def conv_bn(x, conv, bn, relu, skip_out=False, relu_token=None, hand_out_token=F
             # stride-1 3x3: implicit GEMM with LDS im2col, shift and ReLU in its epilogue (csrc/conv3x3.hip); forward and
             # input gradient on the kernel, weight gradient with the library
             return conv3x3_ext.conv3x3(x, w, shift, relu=relu, hand_out_token=hand_out_token and relu, in_token=relu_token)
+        elif conv3x3_ext.ENABLED_F32 and not torch.is_autocast_enabled() and not conv3x3_ext._autocast(x) \
+                and conv3x3_ext.supported_f32(x, w, conv.stride, conv.padding, conv.dilation, conv.groups):
+            # the same in fp32 (mdetr_conv3x3_f32: three-way bf16 split); the weight gradient stays on the library
+            return conv3x3_ext.conv3x3(x, w, shift, relu=relu, hand_out_token=hand_out_token and relu, in_token=relu_token)
         elif relu and bias_act_ext.ENABLED and (x.is_cuda or bias_act_ext._backend is not None):
             # the shift and the ReLU in one pass behind the library convolution (csrc/bias_act.hip) instead of the
             # library's own bias kernel plus a clamp

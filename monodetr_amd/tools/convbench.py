@@ -3,6 +3,7 @@ library convolutions they replace (MIOpen through aten), at the shapes of the tr
 channels_last.  TFLOP/s = 2 B OH OW K K C N / t; `frac_mfma` against the 2.5 PFLOP/s dense bf16 rate.
 
     python -m monodetr_amd.tools.convbench [--iters 20] [--only wgrad|strided|stem]
+    python -m monodetr_amd.tools.convbench --dtype fp32 [--runs 3]      (the fp32 form of conv3x3.hip against the library: `fp32_rows`)
 """
 import argparse
 import json
@@ -17,14 +18,58 @@ def rec(ms, flops):
     return dict(ms=round(ms, 4), TFLOPs=round(flops / ms / 1e9, 1), frac_mfma=round(flops / (ms * 1e-3) / 2.5e15, 4))
 
 
+def fp32_rows(a, dev, B):
+    """--dtype fp32: the fp32 form of csrc/conv3x3.hip (mdetr_conv3x3_f32) against the library route of an fp32 stride-1 3x3 convolution
+    -- forward with the library's bias and ReLU passes, and the input gradient -- in one process, as graph replays over two operand
+    sets: per row the median of --runs captures (best replay of each) with the spread, and the fraction of the six-term matrix-instruction
+    bound 6 x flops / 2.5 PFLOP/s the kernel reaches."""
+    import statistics
+    from monodetr_amd import conv3x3_ext
+    from .gemmbench import graph_time
+    conv3x3_ext.ENABLED_F32 = True
+    shapes = (("layer1", 64, 96, 320), ("layer2", 128, 48, 160), ("layer3", 256, 24, 80), ("layer4", 512, 12, 40), ("depth_head", 256, 24, 80))
+    res, nsets, reps = {}, 2, max(4, a.iters)
+
+    def row(f, flops):
+        us = sorted(graph_time(f, nsets, reps) for _ in range(a.runs))
+        med = statistics.median(us)
+        return dict(us=round(med, 2), spread_us=[us[0], us[-1]], TFLOPs=round(flops / med / 1e6, 1), frac_six_term_mfma=round(6.0 * flops / (med * 1e-6) / 2.5e15, 4))
+
+    done = set()
+    for tag, C, H, W in shapes:
+        if (C, H, W) in done:                                           # (the depth head's 256 -> 256 at 24 x 80 is layer3's problem)
+            res["f32_%s" % tag] = "same problem as layer3"
+            continue
+        done.add((C, H, W))
+        flops = 2.0 * B * H * W * 9 * C * C
+        xs = [(torch.randn(B, H, W, C, device=dev) * 0.5).permute(0, 3, 1, 2) for _ in range(nsets)]
+        dys = [torch.randn(B, H, W, C, device=dev).permute(0, 3, 1, 2) for _ in range(nsets)]
+        w = (torch.randn(C, 3, 3, C, device=dev) / (3.0 * C ** 0.5)).permute(0, 3, 1, 2)
+        sh = torch.randn(C, device=dev) * 0.5
+        assert conv3x3_ext.supported_f32(xs[0], w)
+        wo, wt = conv3x3_ext._ohwi(w), conv3x3_ext._ohwi(w).permute(3, 1, 2, 0).contiguous()
+        res["f32_fwd_%s_kernel" % tag] = row(lambda i: conv3x3_ext._launch(xs[i], wo, sh, True), flops)
+        res["f32_fwd_%s_library" % tag] = row(lambda i: F.relu_(F.conv2d(xs[i], w, sh, padding=1)), flops)
+        res["f32_dgrad_%s_kernel" % tag] = row(lambda i: conv3x3_ext._launch(dys[i], wt, None, False, mirror=True), flops)
+        res["f32_dgrad_%s_library" % tag] = row(lambda i: torch.ops.aten.convolution_backward(
+            dys[i], xs[i], w, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, (True, False, False)), flops)
+        res["f32_%s_plan" % tag] = conv3x3_ext._lib().mdetr_conv3x3_f32_plan(B, H, W, C)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--only", default="")
+    ap.add_argument("--dtype", default="bf16", choices=("bf16", "fp32"))
+    ap.add_argument("--runs", type=int, default=3, help="--dtype fp32: graph captures per row (median and spread are reported)")
     a = ap.parse_args()
     dev, B = "cuda", a.batch
     from monodetr_amd import conv3x3_ext, conv_taps_ext, conv_wgrad_ext
+    if a.dtype == "fp32":
+        print(json.dumps(fp32_rows(a, dev, B)))
+        return
     conv_wgrad_ext.ENABLED = True
     res = {}
 
