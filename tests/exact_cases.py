@@ -97,6 +97,9 @@ def _ordered(t):
     if t.dtype == BF16:
         i = t.contiguous().view(torch.int16).to(torch.int64)
         return torch.where(i < 0, -(i & 0x7FFF), i)
+    if t.dtype == torch.float64:
+        i = t.contiguous().view(torch.int64)
+        return torch.where(i < 0, -(i & 0x7FFFFFFFFFFFFFFF), i)
     i = t.contiguous().view(torch.int32).to(torch.int64)
     return torch.where(i < 0, -(i & 0x7FFFFFFF), i)
 
