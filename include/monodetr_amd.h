@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MDETR_ABI_VERSION 15
+#define MDETR_ABI_VERSION 16
 
 /* element types of the floating-point tensors */
 #define MDETR_F32 0
@@ -695,6 +695,17 @@ int mdetr_conv_stem(const void *x, const void *w_packed, const float *shift, voi
 int mdetr_conv_wgrad_chunks(int B, int H, int W, int C, int OH, int OW, int N, int K, int SI);
 int mdetr_conv_wgrad(const void *x, const void *dy, float *partial, int64_t partial_floats, int B, int H, int W, int C, int OH, int OW, int N,
                      int K, int SI, int device, void *stream);
+/* The fp32 form (ABI 16; csrc/conv_wgrad.hip, conv_wgrad_f32_kernel) for the 3x3 / stride-1 convolutions of the fp32 configurations
+ * (Bottleneck.conv2, the depth head's 3x3): x, dy and the partials are fp32.  Every operand element is split once into three bf16
+ * parts (hi, mid, lo) on its way into LDS and a product is six matrix-instruction terms, small ones first, into one fp32 accumulator
+ * -- fp32-accurate (what is dropped is below 2^-24 of |dy||x| per product).  Same argument order, partial layout and chunk-sum
+ * contract as mdetr_conv_wgrad; deterministic, no atomics.  An infinite operand yields NaN (x - bf16(x)), no fix-up pass.
+ *   K == 3, SI == 1, OH == H, OW == W only;  x  fp32 [B, H, W, C], C % 64 == 0;  dy  fp32 [B, H, W, N], N % 32 == 0; both 16-byte
+ *   aligned;  B H W C and B H W N below 2^29 elements (32-bit byte offsets), 9 N C below 2^28.  Anything else: MDETR_E_ARG, and
+ *   mdetr_conv_wgrad_f32_chunks returns 0.  MDETR_TUNE key conv_wgrad_wgs (workgroups to aim for) applies as to the bf16 entry. */
+int mdetr_conv_wgrad_f32_chunks(int B, int H, int W, int C, int OH, int OW, int N, int K, int SI);
+int mdetr_conv_wgrad_f32(const void *x, const void *dy, float *partial, int64_t partial_floats, int B, int H, int W, int C, int OH, int OW, int N,
+                         int K, int SI, int device, void *stream);
 
 /*
  * Weight AND bias gradient of a token-wise linear layer y = x W^T + b over T token rows (autograd of the nn.Linear / 1x1

@@ -1,7 +1,8 @@
 """``conv3x3(x, weight, shift, relu)``: 3x3 / stride 1 / pad 1 convolution of a channels_last bf16 activation with the folded
 frozen-BN shift and the ReLU in its epilogue (csrc/conv3x3.hip through ``mdetr_conv3x3_forward``): forward and input gradient
 run on the kernel, the weight gradient on csrc/conv_wgrad.hip (conv_wgrad_ext).  With MDETR_CONV3X3_F32=1 fp32 channels_last tensors
-take the fp32 form of the kernel (``mdetr_conv3x3_f32``) for forward and input gradient; their weight gradient stays on the library."""
+take the fp32 form of the kernel (``mdetr_conv3x3_f32``) for forward and input gradient; their weight gradient is the library's, or with
+MDETR_CONV_WGRAD_F32=1 the fp32 form of csrc/conv_wgrad.hip (``mdetr_conv_wgrad_f32``)."""
 import os
 
 import torch
@@ -12,8 +13,8 @@ _backend = None               # tests substitute the CPU emulation of the same k
 # MDETR_CONV3X3=1 routes the backbone's stride-1 3x3 convolutions through the kernel; on the committed bf16 list of kernel_families.py
 ENABLED = os.environ.get("MDETR_CONV3X3") == "1"
 # MDETR_CONV3X3_F32=1: FP32 channels_last activations take the fp32 form of the same kernel (mdetr_conv3x3_f32: operands split three
-# ways into bf16, six matrix-instruction terms -- fp32-accurate), forward and input gradient; the weight gradient stays on the library
-# (csrc/conv_wgrad.hip is bf16-only).  A family of its own, opt-in, on no committed list.
+# ways into bf16, six matrix-instruction terms -- fp32-accurate), forward and input gradient; the weight gradient is the library's unless
+# MDETR_CONV_WGRAD_F32=1 (conv_wgrad_ext.supported_f32: the fp32 form of csrc/conv_wgrad.hip).  A family of its own, opt-in, on no committed list.
 ENABLED_F32 = os.environ.get("MDETR_CONV3X3_F32") == "1"
 
 
@@ -142,6 +143,8 @@ class _Conv3x3(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             from . import conv_wgrad_ext
             if conv_wgrad_ext.supported(x, dy, 3, 1):                    # csrc/conv_wgrad.hip: split-K over pixel tiles on the matrix cores
+                dw = conv_wgrad_ext.weight_gradient(x, dy, 3, 1, weight.dtype, like=weight)
+            elif weight.dtype == torch.float32 and conv_wgrad_ext.supported_f32(x, dy, 3, 1):     # its fp32 form (MDETR_CONV_WGRAD_F32=1)
                 dw = conv_wgrad_ext.weight_gradient(x, dy, 3, 1, weight.dtype, like=weight)
             else:
                 dw = torch.ops.aten.convolution_backward(dy, x, weight, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, (False, True, False))[1]

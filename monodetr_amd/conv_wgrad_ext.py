@@ -1,6 +1,7 @@
 """``weight_gradient(x, dy, k, stride, dtype)``: dW of a 3x3 (stride 1 / 2, pad 1) or 1x1 (stride 2) convolution from the
 channels_last bf16 activation and output gradient (csrc/conv_wgrad.hip through ``mdetr_conv_wgrad``: split-K over pixel tiles
-on the matrix cores; the per-chunk partial gradients are added in a fixed order by csrc/colsum.hip, one rounding)."""
+on the matrix cores; the per-chunk partial gradients are added in a fixed order by csrc/colsum.hip, one rounding).  fp32 operands
+of a 3x3 / stride-1 convolution take the fp32 form of the kernel (``mdetr_conv_wgrad_f32``, MDETR_CONV_WGRAD_F32=1)."""
 import os
 
 import torch
@@ -24,6 +25,33 @@ def supported(x, dy, k, stride):
             and dy.is_contiguous(memory_format=torch.channels_last) and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0)
 
 
+# Which fp32 shape classes take the kernel: tools/convbench --dtype fp32 --only wgrad (profiles/r10a_convbench_fp32_wgrad.json; kernel +
+# chunk sum against aten.convolution_backward, B = 8, medians of 3 captures [min, max], us):
+#   layer1   64 ch, 96 x 320   208.4 [208.0, 210.6]  against  184.3 [178.7, 192.9]   behind: N = 64 fills half of the 128-row dY block
+#   layer2  128 ch, 48 x 160   118.9 [118.2, 119.2]  against  164.4 [159.7, 171.5]   ahead
+#   layer3  256 ch, 24 x 80    111.9 [111.7, 113.1]  against  163.7 [160.9, 172.4]   ahead (the depth head's 3x3 is this problem)
+#   layer4  512 ch, 12 x 40    188.6 [187.7, 188.7]  against  163.6 [161.9, 167.3]   behind: 4 x 8 weight blocks x 3 tap rows leave 2 chunks,
+#                                                                                   192 workgroups of 24 tiles each on 256 CUs
+# A class whose median is not ahead of the library's own [min, max] goes back to the library: fewer than 128 output channels, or more
+# than 8 (128 n x 64 c) weight blocks (layer3 has 8, layer4 32; nothing between them was measured, so nothing between them is admitted).
+_F32_MIN_N = 128
+_F32_MAX_BLOCKS = 8
+
+
+def supported_f32(x, dy, k, stride):
+    """fp32 channels_last operands of a 3x3 / stride-1 convolution within the entry's limits (C % 64 == 0, N % 32 == 0, 16-byte aligned,
+    B H W C and B H W N below 2^29 elements, 9 N C below 2^28) and the measured shape rule above, with the family MDETR_CONV_WGRAD_F32
+    on -- also under the emulated kernel (tests): the family alone decides, so that fp32 convolutions keep the library's weight
+    gradient without it."""
+    return (ENABLED_CONV_F32 and (x.is_cuda or _backend is not None) and x.dim() == 4 and dy.dim() == 4 and x.dtype == torch.float32
+            and dy.dtype == torch.float32 and k == 3 and stride == 1 and x.shape[1] % 64 == 0 and dy.shape[1] % 32 == 0
+            and x.numel() > 0 and dy.numel() > 0 and x.shape[0] == dy.shape[0] and tuple(x.shape[2:]) == tuple(dy.shape[2:])
+            and x.numel() < (1 << 29) and dy.numel() < (1 << 29) and dy.shape[1] * 9 * x.shape[1] < (1 << 28)
+            and dy.shape[1] >= _F32_MIN_N and ((dy.shape[1] + 127) // 128) * (x.shape[1] // 64) <= _F32_MAX_BLOCKS
+            and x.is_contiguous(memory_format=torch.channels_last) and dy.is_contiguous(memory_format=torch.channels_last)
+            and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0)
+
+
 # Weight AND bias gradients of token-wise linear layers over tens of thousands of rows (the encoder's 81 600, the backbone's 1x1
 # convolutions) as the 1x1 case of this kernel, the bias gradient riding along (mdetr_token_wgrad), instead of the library's batched
 # split-K product + chunk sum + two-launch column sum: 53 -> 43 us at [81 600, 256] x [81 600, 256], 49 -> 28-36 us on the backbone's
@@ -33,6 +61,11 @@ TOKEN_ROUTE = True
 # operands split three ways into bf16, six matrix-instruction terms -- fp32-accurate) instead of the library's batched product + chunk
 # sum + column sum.  A family of its own: separate from ENABLED (MDETR_CONV_WGRAD) and from linear._TGEMM_F32.  Opt-in, on no committed list.
 ENABLED_F32 = os.environ.get("MDETR_TWGRAD_F32") == "1"
+# MDETR_CONV_WGRAD_F32=1: the weight gradient of the FP32 stride-1 3x3 convolutions through the fp32 form of csrc/conv_wgrad.hip
+# (mdetr_conv_wgrad_f32: operands split three ways into bf16, six matrix-instruction terms -- fp32-accurate) instead of the library's
+# (MIOpen igemm_wrw / CK bwd_weight).  Consulted in conv3x3_ext._Conv3x3.backward only, so in the step it acts together with
+# MDETR_CONV3X3_F32.  A family of its own, opt-in, on no committed list.
+ENABLED_CONV_F32 = os.environ.get("MDETR_CONV_WGRAD_F32") == "1"
 
 
 def _chunk_sum_route(chunk_sums, cuda, cols, dtype):
@@ -119,12 +152,17 @@ def _stolen(like, N, C, k):
 
 
 def weight_gradient(x, dy, k, stride, dtype=torch.bfloat16, like=None):
-    """x [B, C, H, W], dy [B, N, OH, OW] (channels_last bf16) -> dW [N, C, k, k] in ``dtype`` (channels_last strides).
+    """x [B, C, H, W], dy [B, N, OH, OW] (channels_last, both bf16 or -- k = 3, stride 1 -- both fp32) -> dW [N, C, k, k] in ``dtype``
+    (channels_last strides).
     like: the weight the gradient is for; a leaf whose strides are not the result's gets its sum at once, never deferred (chunk_sums.py)."""
     B, C, H, W = x.shape
     _, N, OH, OW = dy.shape
     lib = _lib()
-    chunks = lib.mdetr_conv_wgrad_chunks(B, H, W, C, OH, OW, N, k, stride)
+    if x.dtype != dy.dtype or x.dtype not in (torch.bfloat16, torch.float32):
+        raise RuntimeError("conv_wgrad: operands of one dtype, bf16 or fp32 (got %s, %s)" % (x.dtype, dy.dtype))
+    # fp32 operands: the fp32 form of the kernel (three-way bf16 split), same partials and chunk sums
+    entry = "mdetr_conv_wgrad_f32" if x.dtype == torch.float32 else "mdetr_conv_wgrad"
+    chunks = getattr(lib, entry + "_chunks")(B, H, W, C, OH, OW, N, k, stride)
     if chunks <= 0:
         raise RuntimeError("conv_wgrad: unsupported problem")
     cols = N * k * k * C
@@ -136,10 +174,10 @@ def weight_gradient(x, dy, k, stride, dtype=torch.bfloat16, like=None):
         part = W_.get("conv_wgrad", x.device, chunks * cols * 4).view(torch.float32)[:chunks * cols]
     else:
         part = torch.empty(chunks * cols, dtype=torch.float32, device=x.device)
-    rc = lib.mdetr_conv_wgrad(x.data_ptr(), dy.data_ptr(), part.data_ptr(), part.numel(), B, H, W, C, OH, OW, N, k, stride,
-                              x.device.index if cuda else -1, torch.cuda.current_stream(x.device).cuda_stream if cuda else None)
+    rc = getattr(lib, entry)(x.data_ptr(), dy.data_ptr(), part.data_ptr(), part.numel(), B, H, W, C, OH, OW, N, k, stride,
+                             x.device.index if cuda else -1, torch.cuda.current_stream(x.device).cuda_stream if cuda else None)
     if rc != 0:
-        _capi.check(rc, "mdetr_conv_wgrad")
+        _capi.check(rc, entry)
     part = part.view(chunks, cols)
     if batched:
         dw = chunk_sums.chunk_sum(part, dtype, defer=_stolen(like, N, C, k))

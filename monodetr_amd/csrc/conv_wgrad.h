@@ -19,4 +19,11 @@ bool conv_wgrad_supported(const ConvWgradDims &d, const void *x, const void *dy)
 int conv_wgrad_chunks(const ConvWgradDims &d);
 hipError_t conv_wgrad_launch(const void *x, const void *dy, float *part, const ConvWgradDims &d, hipStream_t st);
 
+// The fp32 form (conv_wgrad_f32_kernel): x and dy fp32, K = 3, SI = 1 (OH = H, OW = W), DB = 0 only; B H W C and B H W N below 2^29
+// elements.  Operands are split into three bf16 parts on their way into LDS (mdetr_split.h): an infinite operand yields NaN.
+// Same partials: fp32 [chunks][N][3][3][C], chunks = conv_wgrad_f32_chunks(d).
+bool conv_wgrad_f32_supported(const ConvWgradDims &d, const void *x, const void *dy);
+int conv_wgrad_f32_chunks(const ConvWgradDims &d);
+hipError_t conv_wgrad_f32_launch(const void *x, const void *dy, float *part, const ConvWgradDims &d, hipStream_t st);
+
 }  // namespace mdetr

@@ -22,6 +22,8 @@
 // Output: per-chunk partial gradients P[chunk][n][t][e][c] in fp32; colsum.hip adds the chunks in a fixed order and rounds once
 // into the parameter's dtype (deterministic, no atomics).
 // Algorithmic bytes = 2 B (H W C + OH OW N) + 4 TR TS N C;  flops = 2 B OH OW TR TS C N.  MFMA-bound by design.
+// The fp32 form of the 3x3 / stride-1 case (mdetr_conv_wgrad_f32: fp32 x and dy, three-way bf16 split, six terms per product) is the
+// sibling kernel conv_wgrad_f32_kernel further down.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -31,7 +33,8 @@
 #include "conv_wgrad.h"
 #include "mdetr_tune.h"
 #include "mdetr_transpose.h"
-#include "msda.h"       // profile scopes
+#include "mdetr_split.h"
+#include "msda.h"      // profile scopes
 
 namespace mdetr {
 namespace {
@@ -248,12 +251,190 @@ hipError_t launch(const void *x, const void *dy, float *part, WgradGeom g, hipSt
     return hipGetLastError();
 }
 
-WgradGeom geometry(const ConvWgradDims &d)
+// ---- The fp32 form (mdetr_conv_wgrad_f32): x and dy fp32, 3 x 3 taps, stride 1.  A sibling kernel -- the bf16 kernel above has no
+// run-time or compile-time flag for it.  The workgroup (tap row t, 128 n, 64 c, a chunk of 8 x 16 pixel tiles), the loading tasks,
+// the buffer-resource loads, the single LDS buffer with the next tile's loads in flight and the partials' layout are the bf16
+// kernel's.  What differs: a lane's 8 row x 8 channel block is 16 loads of 16 bytes (4 fp32 each); every piece is split once
+// (split4, mdetr_split.h) into hi / mid / lo bf16 parts, each part's 8 x 8 block is transposed and stored into ITS plane of LDS --
+// three planes of the bf16 kernel's row geometry (dYt 128 x 17 slots, Xt 64 x 19 slots: 3 x 54 272 = 162 816 bytes, one workgroup
+// per CU) -- and a k-step reads the dY triple once and the X triple per tap column and issues the six terms
+//   lo.hi  hi.lo  mid.mid  mid.hi  hi.mid  hi.hi        (dY part x X part, small ones first)
+// into the ONE accumulator of that tap column.  What is dropped (mid.lo, lo.mid, lo.lo) is below 2^-24 of |dy||x| per product.
+// An infinite operand yields NaN (x - bf16(x)), as in the other fp32 forms.  One tile in flight (64 staging registers).
+constexpr int kCols32 = 16;                                                  // (independent of MDETR_CONV_WGRAD_COLS: three planes of 32 columns do not fit)
+constexpr int kDyStride32 = kCols32 + 1, kXC32 = kCols32 + 2, kXStride32 = kXC32 | 1;
+constexpr int kDyPlane32 = kNB * kDyStride32, kXPlane32 = kCB * kXStride32;  // 16-byte slots of one plane
+constexpr size_t kLds32 = static_cast<size_t>(3) * (kDyPlane32 + kXPlane32) * 16;
+static_assert(kLds32 == 162816 && kLds32 <= 160 * 1024, "three planes of the 128 x 64 tile: one workgroup per CU");
+
+__global__ __launch_bounds__(kThreadsG)
+void conv_wgrad_f32_kernel(const float *__restrict__ x, const float *__restrict__ dy, float *__restrict__ part, const WgradGeom g)
+{
+    constexpr int TS = 3;
+    MDETR_DYNAMIC_LDS(unsigned char, wgrad32_smem);
+    bf16x8 *dyt = reinterpret_cast<bf16x8 *>(wgrad32_smem);                  // [3 planes][kNB][kDyStride32]
+    bf16x8 *xt = dyt + 3 * kDyPlane32;                                       // [3 planes][kCB][kXStride32]
+    const ConvWgradDims &d = g.d;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
+    const int nsub = wave & 3, csub = wave >> 2;
+    int id = blockIdx.x;
+    const int chunk = id % g.chunks; id /= g.chunks;
+    const int t = id % TS; id /= TS;                                         // tap row
+    const int cblk = id % g.cblocks; const int nblk = id / g.cblocks;
+    const int n0 = nblk * kNB, c0 = cblk * kCB;
+
+    f32x16 acc[TS];
+#pragma unroll
+    for (int e = 0; e < TS; ++e)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[e][i] = 0.f;
+
+    // ---- loading tasks: the bf16 kernel's (a wave = 16 columns x 4 pieces of 8 channels of one operand, lane = 16 piece + column),
+    // one task per wave: waves 0 - 3 the 18 columns x 64 channels of the X window, waves 4 - 7 the 16 columns x 128 channels of dY
+    constexpr int CGX = (kXC32 + 15) / 16;
+    constexpr int WTASKS = 2 * CGX + 4 * (kCols32 / 16);
+    static_assert(WTASKS == kThreadsG / 64, "one loading task per wave");
+    bf16x8 stage[16];                                                        // 16 bytes = 4 fp32 each (the load moves bits): row i = stage[2 i], stage[2 i + 1]
+    const mdetr_rsrc xr = make_rsrc(x, static_cast<unsigned>(static_cast<int64_t>(d.B) * d.H * d.W * d.C * 4));
+    const mdetr_rsrc yr = make_rsrc(dy, static_cast<unsigned>(static_cast<int64_t>(d.B) * d.OH * d.OW * d.N * 4));
+    const int ci = lane & 15, pi = lane >> 4;
+    const bool is_x = wave < 2 * CGX;                                        // wave-uniform
+    int t_rel, t_ch, t_dst;
+    if (is_x) {
+        const int slot = 16 * (wave >> 1) + ci, piece = 4 * (wave & 1) + pi;
+        t_rel = slot >= kXC32 ? -1 : slot;
+        t_ch = (c0 + piece * 8) * 4;
+        t_dst = piece * 8 * kXStride32 + slot;
+    } else {
+        const int k = wave - 2 * CGX, col = 16 * (k >> 2) + ci, piece = 4 * (k & 3) + pi;
+        t_rel = col;
+        t_ch = n0 + piece * 8 < d.N ? (n0 + piece * 8) * 4 : -1;
+        t_dst = piece * 8 * kDyStride32 + col;
+    }
+    auto fetch = [&](int u) {                                                // global loads of pixel tile u
+        const int ct = u % g.ctiles; u /= g.ctiles;
+        const int band = u % g.bands; const int b = u / g.bands;
+        const int r0 = band * kRows, q0 = ct * kCols32;
+        if (is_x) {
+            const int col = q0 + t_rel - 1;
+            const bool in = t_rel >= 0 && col >= 0 && col < d.W;
+            const unsigned lane_off = in ? static_cast<unsigned>(col * d.C * 4 + t_ch) : 0u;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int row = r0 + i + t - 1;                              // uniform
+                const bool ok = in && row >= 0 && row < d.H;
+                const unsigned so = (row >= 0 && row < d.H) ? static_cast<unsigned>((b * d.H + row) * d.W) * static_cast<unsigned>(d.C * 4) : 0u;
+                stage[2 * i] = rsrc_load_bf16x8(xr, ok ? lane_off : kRsrcOob, so);
+                stage[2 * i + 1] = rsrc_load_bf16x8(xr, ok ? lane_off + 16u : kRsrcOob, so);
+            }
+        } else {
+            const int col = q0 + t_rel;
+            const bool in = col < d.OW && t_ch >= 0;
+            const unsigned lane_off = in ? static_cast<unsigned>(col * d.N * 4 + t_ch) : 0u;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int row = r0 + i;
+                const bool ok = in && row < d.OH;
+                const unsigned so = row < d.OH ? static_cast<unsigned>((b * d.OH + row) * d.OW) * static_cast<unsigned>(d.N * 4) : 0u;
+                stage[2 * i] = rsrc_load_bf16x8(yr, ok ? lane_off : kRsrcOob, so);
+                stage[2 * i + 1] = rsrc_load_bf16x8(yr, ok ? lane_off + 16u : kRsrcOob, so);
+            }
+        }
+    };
+    auto commit = [&]() {                                                    // split once, transpose each part's block into its plane
+        bf16x8 pl[3][8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                float f[4];
+                __builtin_memcpy(f, &stage[2 * i + s], 16);
+                bf16x4 h, m, l;
+                split4(f, h, m, l);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { pl[0][i][4 * s + j] = h[j]; pl[1][i][4 * s + j] = m[j]; pl[2][i][4 * s + j] = l[j]; }
+            }
+        }
+        if (is_x && t_rel < 0) return;                                       // (the window's 18 columns: lanes of the second group beyond it)
+        bf16x8 *dst = is_x ? xt + t_dst : dyt + t_dst;
+        const int stride = is_x ? kXStride32 : kDyStride32, plane = is_x ? kXPlane32 : kDyPlane32;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            bf16x8 tr[8];
+            transpose8x8(pl[p], tr);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) dst[p * plane + q * stride] = tr[q];
+        }
+    };
+    auto products = [&]() {
+        const bf16x8 *ap = dyt + (nsub * 32 + l31) * kDyStride32 + half;
+        const bf16x8 *bp = xt + (csub * 32 + l31) * kXStride32 + half;
+        constexpr int term_y[6] = {2, 0, 1, 1, 0, 0}, term_x[6] = {0, 2, 1, 0, 1, 0};       // 0 hi, 1 mid, 2 lo
+#pragma unroll 2
+        for (int ks = 0; ks < kCols32 / 2; ++ks) {
+            bf16x8 a[3], b[TS][3];                                           // this half-wave's column of the k-step: q = 2 ks + half
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+                a[p] = ap[p * kDyPlane32 + 2 * ks];
+#pragma unroll
+                for (int e = 0; e < TS; ++e) b[e][p] = bp[p * kXPlane32 + 2 * ks + e];
+            }
+#pragma unroll
+            for (int k = 0; k < 6; ++k)                                      // term by term over the tap columns: every accumulator sees the order above
+#pragma unroll
+                for (int e = 0; e < TS; ++e) acc[e] = mfma_bf16(a[term_y[k]], b[e][term_x[k]], acc[e]);
+        }
+    };
+
+    // tile u's loads were issued one step before its products; one LDS buffer
+    int u = chunk;
+    if (u < g.units) fetch(u);
+    while (u < g.units) {
+        __syncthreads();                                                     // the previous tile's LDS reads are done
+        commit();
+        const int nu = u + g.chunks;
+        if (nu < g.units) fetch(nu);                                         // in flight during this tile's products
+        __syncthreads();
+        products();
+        u = nu;
+    }
+
+    // ---- epilogue: the bf16 kernel's
+    const int c = c0 + csub * 32 + l31;
+    float *pp = part + static_cast<int64_t>(chunk) * (static_cast<int64_t>(d.N) * TS * TS * d.C);
+#pragma unroll
+    for (int e = 0; e < TS; ++e)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int n = n0 + nsub * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (n < d.N) pp[((static_cast<int64_t>(n) * TS + t) * TS + e) * d.C + c] = acc[e][r];
+        }
+}
+
+hipError_t launch_f32(const void *x, const void *dy, float *part, WgradGeom g, hipStream_t st)
+{
+    auto kern = conv_wgrad_f32_kernel;
+    static bool attr_set[64] = {};
+    int dev_ = 0;
+    if (hipGetDevice(&dev_) != hipSuccess) dev_ = -1;
+    if (dev_ < 0 || dev_ >= 64 || !attr_set[dev_]) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 static_cast<int>(kLds32));
+        if (e != hipSuccess) return e;
+        if (dev_ >= 0 && dev_ < 64) attr_set[dev_] = true;
+    }
+    const int64_t blocks = static_cast<int64_t>(g.chunks) * 3 * g.cblocks * g.nblocks;
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(kThreadsG), kLds32, st, static_cast<const float *>(x),
+                       static_cast<const float *>(dy), part, g);
+    return hipGetLastError();
+}
+
+WgradGeom geometry(const ConvWgradDims &d, int cols = kCols)
 {
     WgradGeom g;
     g.d = d;
     g.bands = (d.OH + kRows - 1) / kRows;
-    g.ctiles = (d.OW + kCols - 1) / kCols;
+    g.ctiles = (d.OW + cols - 1) / cols;
     g.units = d.B * g.bands * g.ctiles;
     g.nblocks = (d.N + kNB - 1) / kNB;
     g.cblocks = d.C / kCB;
@@ -294,6 +475,26 @@ hipError_t conv_wgrad_launch(const void *x, const void *dy, float *part, const C
                       (2.0 * d.B * (static_cast<double>(d.H) * d.W * d.C + static_cast<double>(d.OH) * d.OW * d.N) + 4.0 * g.chunks * d.K * d.K * d.N * d.C) / 1e3);
     if (d.K == 3) return d.SI == 1 ? launch<1, 3>(x, dy, part, g, st) : launch<2, 3>(x, dy, part, g, st);
     return d.SI == 1 ? launch<1, 1>(x, dy, part, g, st) : launch<2, 1>(x, dy, part, g, st);
+}
+
+bool conv_wgrad_f32_supported(const ConvWgradDims &d, const void *x, const void *dy)
+{
+    const auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    // (fp32 elements: 2^29 of them are 2^31 bytes -- the 32-bit byte offsets of the buffer-resource loads)
+    return d.K == 3 && d.SI == 1 && d.DB == 0 && d.B > 0 && d.H > 0 && d.W > 0 && d.OH == d.H && d.OW == d.W && d.C > 0 && d.C % 64 == 0 &&
+           d.N > 0 && d.N % 32 == 0 && al(x) && al(dy) && static_cast<int64_t>(d.N) * 9 * d.C < (1ll << 28) &&
+           static_cast<int64_t>(d.B) * d.H * d.W * d.C < (1ll << 29) && static_cast<int64_t>(d.B) * d.H * d.W * d.N < (1ll << 29);
+}
+
+int conv_wgrad_f32_chunks(const ConvWgradDims &d) { return geometry(d, kCols32).chunks; }
+
+hipError_t conv_wgrad_f32_launch(const void *x, const void *dy, float *part, const ConvWgradDims &d, hipStream_t st)
+{
+    const WgradGeom g = geometry(d, kCols32);
+    ProfileScope prof(9, conv_mflop(static_cast<int64_t>(d.B) * d.OH * d.OW, static_cast<int64_t>(d.C) * d.N * 9), st,
+                      2.0 * d.B * d.OH * d.OW * d.C * d.N * 9 / 1e6,
+                      (4.0 * d.B * (static_cast<double>(d.H) * d.W * d.C + static_cast<double>(d.OH) * d.OW * d.N) + 4.0 * g.chunks * 9 * d.N * d.C) / 1e3);
+    return launch_f32(x, dy, part, g, st);
 }
 
 }  // namespace mdetr

@@ -3,7 +3,7 @@ library convolutions they replace (MIOpen through aten), at the shapes of the tr
 channels_last.  TFLOP/s = 2 B OH OW K K C N / t; `frac_mfma` against the 2.5 PFLOP/s dense bf16 rate.
 
     python -m monodetr_amd.tools.convbench [--iters 20] [--only wgrad|strided|stem]
-    python -m monodetr_amd.tools.convbench --dtype fp32 [--runs 3]      (the fp32 form of conv3x3.hip against the library: `fp32_rows`)
+    python -m monodetr_amd.tools.convbench --dtype fp32 [--runs 3]      (the fp32 forms of conv3x3.hip / conv_wgrad.hip against the library: `fp32_rows`)
 """
 import argparse
 import json
@@ -19,14 +19,16 @@ def rec(ms, flops):
 
 
 def fp32_rows(a, dev, B):
-    """--dtype fp32: the fp32 form of csrc/conv3x3.hip (mdetr_conv3x3_f32) against the library route of an fp32 stride-1 3x3 convolution
-    -- forward with the library's bias and ReLU passes, and the input gradient -- in one process, as graph replays over two operand
+    """--dtype fp32: the fp32 forms of csrc/conv3x3.hip (mdetr_conv3x3_f32) and csrc/conv_wgrad.hip (mdetr_conv_wgrad_f32 + its chunk sum)
+    against the library route of an fp32 stride-1 3x3 convolution -- forward with the library's bias and ReLU passes, the input
+    gradient and the weight gradient -- in one process, as graph replays over two operand
     sets: per row the median of --runs captures (best replay of each) with the spread, and the fraction of the six-term matrix-instruction
     bound 6 x flops / 2.5 PFLOP/s the kernel reaches."""
     import statistics
-    from monodetr_amd import conv3x3_ext
+    from monodetr_amd import conv3x3_ext, conv_wgrad_ext
     from .gemmbench import graph_time
     conv3x3_ext.ENABLED_F32 = True
+    conv_wgrad_ext.ENABLED_CONV_F32 = True
     shapes = (("layer1", 64, 96, 320), ("layer2", 128, 48, 160), ("layer3", 256, 24, 80), ("layer4", 512, 12, 40), ("depth_head", 256, 24, 80))
     res, nsets, reps = {}, 2, max(4, a.iters)
 
@@ -48,12 +50,19 @@ def fp32_rows(a, dev, B):
         sh = torch.randn(C, device=dev) * 0.5
         assert conv3x3_ext.supported_f32(xs[0], w)
         wo, wt = conv3x3_ext._ohwi(w), conv3x3_ext._ohwi(w).permute(3, 1, 2, 0).contiguous()
-        res["f32_fwd_%s_kernel" % tag] = row(lambda i: conv3x3_ext._launch(xs[i], wo, sh, True), flops)
-        res["f32_fwd_%s_library" % tag] = row(lambda i: F.relu_(F.conv2d(xs[i], w, sh, padding=1)), flops)
-        res["f32_dgrad_%s_kernel" % tag] = row(lambda i: conv3x3_ext._launch(dys[i], wt, None, False, mirror=True), flops)
-        res["f32_dgrad_%s_library" % tag] = row(lambda i: torch.ops.aten.convolution_backward(
-            dys[i], xs[i], w, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, (True, False, False)), flops)
-        res["f32_%s_plan" % tag] = conv3x3_ext._lib().mdetr_conv3x3_f32_plan(B, H, W, C)
+        if a.only != "wgrad":                                          # (--only wgrad: the weight-gradient rows alone)
+            res["f32_fwd_%s_kernel" % tag] = row(lambda i: conv3x3_ext._launch(xs[i], wo, sh, True), flops)
+            res["f32_fwd_%s_library" % tag] = row(lambda i: F.relu_(F.conv2d(xs[i], w, sh, padding=1)), flops)
+            res["f32_dgrad_%s_kernel" % tag] = row(lambda i: conv3x3_ext._launch(dys[i], wt, None, False, mirror=True), flops)
+            res["f32_dgrad_%s_library" % tag] = row(lambda i: torch.ops.aten.convolution_backward(
+                dys[i], xs[i], w, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, (True, False, False)), flops)
+            res["f32_%s_plan" % tag] = conv3x3_ext._lib().mdetr_conv3x3_f32_plan(B, H, W, C)
+        # the weight gradient: the fp32 form of csrc/conv_wgrad.hip (mdetr_conv_wgrad_f32) + the sum over its chunks against the library's
+        res["f32_wgrad_%s_routed_to_kernel" % tag] = bool(conv_wgrad_ext.supported_f32(xs[0], dys[0], 3, 1))     # (the shape rule; both are timed)
+        res["f32_wgrad_%s_kernel" % tag] = row(lambda i: conv_wgrad_ext.weight_gradient(xs[i], dys[i], 3, 1, torch.float32), flops)
+        res["f32_wgrad_%s_library" % tag] = row(lambda i: torch.ops.aten.convolution_backward(
+            dys[i], xs[i], w, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, (False, True, False)), flops)
+        res["f32_wgrad_%s_chunks" % tag] = conv_wgrad_ext._lib().mdetr_conv_wgrad_f32_chunks(B, H, W, C, H, W, C, 3, 1)
     return res
 
 
