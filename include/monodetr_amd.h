@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MDETR_ABI_VERSION 16
+#define MDETR_ABI_VERSION 17
 
 /* element types of the floating-point tensors */
 #define MDETR_F32 0
@@ -673,6 +673,28 @@ int mdetr_conv_taps_split(const void *x, const void *w, const float *shift, floa
  *   dx  bf16 [B, H, W, C], C % 32 == 0;  OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1
  */
 int mdetr_conv_dgrad_s2(const void *dy, const void *wt, void *dx, int B, int OH, int OW, int N, int H, int W, int C, int K, int device, void *stream);
+
+/*
+ * The fp32 forms of the three entries above (ABI 17; csrc/conv_taps.hip, conv_taps_f32_body) for the 3x3 / stride-2 / pad-1
+ * convolutions of the fp32 configurations: x / dy, w / wt, shift, y / dx and the partials are fp32.  Each operand is split once into
+ * three bf16 parts (hi, mid, lo) on its way into LDS and a product is six matrix-instruction terms, small ones first, into one fp32
+ * accumulator -- fp32-accurate (what is dropped is below 2^-24 of |x||w| per product); shift and ReLU are applied in fp32 and the
+ * result is written without any further rounding.  Deterministic, no atomics.  An infinite operand yields NaN (x - bf16(x)).
+ *   mdetr_conv_taps_f32        dims as mdetr_conv_taps with SI = 2, TR = TS = 3, PT = PL = 1, OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1
+ *                              (the 1x1 / stride-2 shortcut is a gather and a token GEMM in fp32: refused); C % 64 == 0, N % 32 == 0;
+ *                              x, w, y 16-byte aligned, weight and output strides multiples of 4 elements; B H W C < 2^29
+ *   mdetr_conv_taps_f32_split  the same with the contraction split: fp32 partials [ksplit][B][OH][OW][N] (split 0 carries the shift),
+ *                              summed by the caller in a fixed order; C % (16 ksplit) == 0, 2 <= ksplit <= 64
+ *   mdetr_conv_dgrad_s2_f32    K == 3; dy [B, OH, OW, N], N % 64 == 0; wt [C, 3, 3, N]; dx [B, H, W, C], C % 32 == 0, every element
+ *                              written exactly once; all 16-byte aligned; B OH OW N < 2^29, B H W C < 2^30
+ * Anything else: MDETR_E_ARG.  An empty batch returns 0 without a launch.  MDETR_TUNE keys conv_taps_f32_nb (1, 2 or 4: output
+ * channels per workgroup / 32) and conv_taps_f32_rows (4, or 2: output rows per forward workgroup) force the geometry; the bf16 key
+ * does not apply.
+ */
+int mdetr_conv_taps_f32(const void *x, const void *w, const float *shift, void *y, const int64_t *dims, int relu, int device, void *stream);
+int mdetr_conv_taps_f32_split(const void *x, const void *w, const float *shift, float *partial, int64_t partial_floats, const int64_t *dims,
+                              int ksplit, int device, void *stream);
+int mdetr_conv_dgrad_s2_f32(const void *dy, const void *wt, void *dx, int B, int OH, int OW, int N, int H, int W, int C, int K, int device, void *stream);
 
 /*
  * The ResNet stem (torchvision ResNet.conv1 -> bn1 -> relu behind lib/models/monodetr/backbone.py:93-106; frozen: forward only):

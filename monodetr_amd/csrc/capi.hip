@@ -859,6 +859,85 @@ int mdetr_conv_dgrad_s2(const void *dy, const void *wt, void *dx, int B, int OH,
     return MDETR_OK;
 }
 
+// the 23 dims of mdetr_conv_taps; false (with the error set) on a bad size
+static bool taps_dims(const char *who, const int64_t *dims, mdetr::ConvTapsDims &d)
+{
+    if (!dims) { fail(MDETR_E_ARG, "%s: null dims", who); return false; }
+    for (int i = 0; i < 12; ++i)
+        if (dims[i] < 0 || dims[i] > (1ll << 30)) { fail(MDETR_E_ARG, "%s: bad size dims[%d] = %lld", who, i, static_cast<long long>(dims[i])); return false; }
+    for (int i = 12; i < 16; ++i)                                           // tap offsets and steps: checked before they are narrowed to int
+        if (dims[i] < -2 || dims[i] > 2) { fail(MDETR_E_ARG, "%s: bad tap offset / step dims[%d] = %lld", who, i, static_cast<long long>(dims[i])); return false; }
+    d.B = static_cast<int>(dims[0]); d.H = static_cast<int>(dims[1]); d.W = static_cast<int>(dims[2]); d.C = static_cast<int>(dims[3]);
+    d.OH = static_cast<int>(dims[4]); d.OW = static_cast<int>(dims[5]); d.N = static_cast<int>(dims[6]);
+    d.SI = static_cast<int>(dims[7]); d.TR = static_cast<int>(dims[8]); d.TS = static_cast<int>(dims[9]);
+    d.PT = static_cast<int>(dims[10]); d.PL = static_cast<int>(dims[11]);
+    d.ta0 = static_cast<int>(dims[12]); d.ta_step = static_cast<int>(dims[13]); d.te0 = static_cast<int>(dims[14]); d.te_step = static_cast<int>(dims[15]);
+    d.y_off = dims[16]; d.y_sb = dims[17]; d.y_sr = dims[18]; d.y_sc = dims[19];
+    d.w_sn = dims[20]; d.w_sa = dims[21]; d.w_se = dims[22];
+    return true;
+}
+
+// the forward taps must stay inside the 3x3 weight the strides describe
+static bool taps_in_weight(const mdetr::ConvTapsDims &d)
+{
+    const auto in = [](int t0, int step) { return t0 >= 0 && t0 <= 2 && t0 + 2 * step >= 0 && t0 + 2 * step <= 2; };
+    return in(d.ta0, d.ta_step) && in(d.te0, d.te_step) && d.w_sn > 0 && d.w_sa > 0 && d.w_se > 0;
+}
+
+int mdetr_conv_taps_f32(const void *x, const void *w, const float *shift, void *y, const int64_t *dims, int relu, int device, void *stream)
+{
+    const char *who = "mdetr_conv_taps_f32";
+    mdetr::ConvTapsDims d;
+    if (!taps_dims(who, dims, d)) return MDETR_E_ARG;
+    if (d.B == 0 || d.OH == 0 || d.OW == 0) return MDETR_OK;
+    if (!x || !w || !y) return fail(MDETR_E_ARG, "%s: null pointer", who);
+    if (!mdetr::conv_taps_f32_supported(d, x, w, y) || !taps_in_weight(d))
+        return fail(MDETR_E_ARG, "%s: needs the 3x3 / stride-2 / pad-1 form (taps %dx%d stride %d), C=%d %% 64, N=%d %% 32, 16-byte aligned x / w / y, strides in "
+                                 "whole 16-byte units, B H W C below 2^29", who, d.TR, d.TS, d.SI, d.C, d.N);
+    DeviceScope dev(device);
+    if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "%s: set device %d: %s", who, device, hipGetErrorString(dev.err));
+    const hipError_t e = mdetr::conv_taps_f32_launch(x, w, shift, y, d, relu != 0, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MDETR_E_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+    return MDETR_OK;
+}
+
+int mdetr_conv_taps_f32_split(const void *x, const void *w, const float *shift, float *partial, int64_t partial_floats, const int64_t *dims,
+                              int ksplit, int device, void *stream)
+{
+    const char *who = "mdetr_conv_taps_f32_split";
+    mdetr::ConvTapsDims d;
+    if (!taps_dims(who, dims, d)) return MDETR_E_ARG;
+    d.y_off = 0; d.y_sb = static_cast<int64_t>(d.OH) * d.OW * d.N; d.y_sr = static_cast<int64_t>(d.OW) * d.N; d.y_sc = d.N;
+    if (d.B == 0 || d.OH == 0 || d.OW == 0) return MDETR_OK;
+    if (!x || !w || !partial) return fail(MDETR_E_ARG, "%s: null pointer", who);
+    if (!mdetr::conv_taps_f32_supported(d, x, w, partial) || !taps_in_weight(d) || !mdetr::conv_taps_f32_split_supported(d, ksplit))
+        return fail(MDETR_E_ARG, "%s: needs the 3x3 / stride-2 / pad-1 form, C %% 64 == 0 and a multiple of 16 x ksplit (C=%d ksplit=%d), 2 <= ksplit <= 64, "
+                                 "N=%d %% 32, 16-byte aligned x / w / partial, B H W C below 2^29", who, d.C, ksplit, d.N);
+    const int64_t need = static_cast<int64_t>(ksplit) * d.B * d.OH * d.OW * d.N;
+    if (partial_floats < need) return fail(MDETR_E_ARG, "%s: partial buffer holds %lld floats, %lld needed", who, static_cast<long long>(partial_floats), static_cast<long long>(need));
+    DeviceScope dev(device);
+    if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "%s: set device %d: %s", who, device, hipGetErrorString(dev.err));
+    const hipError_t e = mdetr::conv_taps_f32_split_launch(x, w, shift, partial, d, ksplit, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MDETR_E_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+    return MDETR_OK;
+}
+
+int mdetr_conv_dgrad_s2_f32(const void *dy, const void *wt, void *dx, int B, int OH, int OW, int N, int H, int W, int C, int K, int device, void *stream)
+{
+    const char *who = "mdetr_conv_dgrad_s2_f32";
+    if (B < 0 || OH < 0 || OW < 0 || H < 0 || W < 0 || N <= 0 || C <= 0) return fail(MDETR_E_ARG, "%s: bad sizes", who);
+    if (B == 0 || H == 0 || W == 0) return MDETR_OK;
+    if (!dy || !wt || !dx) return fail(MDETR_E_ARG, "%s: null pointer", who);
+    if (K != 3 || !mdetr::conv_dgrad_s2_f32_supported(B, OH, OW, N, H, W, C, dy, wt, dx))
+        return fail(MDETR_E_ARG, "%s: needs K == 3, N %% 64 == 0, C %% 32 == 0, OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1, 16-byte aligned dy / wt / dx, "
+                                 "B OH OW N below 2^29 and B H W C below 2^30 (K=%d N=%d C=%d %dx%d -> %dx%d)", who, K, N, C, H, W, OH, OW);
+    DeviceScope dev(device);
+    if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "%s: set device %d: %s", who, device, hipGetErrorString(dev.err));
+    const hipError_t e = mdetr::conv_dgrad_s2_f32_launch(dy, wt, dx, B, OH, OW, N, H, W, C, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MDETR_E_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+    return MDETR_OK;
+}
+
 int mdetr_conv_stem(const void *x, const void *w_packed, const float *shift, void *y, int B, int H, int W, int device, void *stream)
 {
     if (B < 0 || H < 0 || W < 0) return fail(MDETR_E_ARG, "mdetr_conv_stem: bad sizes B=%d H=%d W=%d", B, H, W);

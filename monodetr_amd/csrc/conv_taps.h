@@ -27,4 +27,14 @@ bool conv_taps_split_supported(const ConvTapsDims &d, int ksplit);
 hipError_t conv_taps_split_launch(const void *x, const void *w, const float *shift, float *part, const ConvTapsDims &d, int ksplit, hipStream_t st);
 hipError_t conv_taps_launch(const void *x, const void *w, const float *shift, void *y, const ConvTapsDims &d, bool relu, hipStream_t st);
 
+// The fp32 forms (x / dy, w / wt, shift, y / dx and the partials fp32; three-way bf16 split, six product terms; an infinite operand
+// yields NaN): the 3x3 / stride-2 / pad-1 forward (conv_taps_f32_supported refuses every other tap set), its split-contraction form
+// (C % (16 ksplit) == 0) and the input gradient of the 3x3 / stride-2 convolution.  B H W C < 2^29 (B OH OW N for the gradient).
+bool conv_taps_f32_supported(const ConvTapsDims &d, const void *x, const void *w, const void *y);
+hipError_t conv_taps_f32_launch(const void *x, const void *w, const float *shift, void *y, const ConvTapsDims &d, bool relu, hipStream_t st);
+bool conv_taps_f32_split_supported(const ConvTapsDims &d, int ksplit);
+hipError_t conv_taps_f32_split_launch(const void *x, const void *w, const float *shift, float *part, const ConvTapsDims &d, int ksplit, hipStream_t st);
+bool conv_dgrad_s2_f32_supported(int B, int OH, int OW, int N, int H, int W, int C, const void *dy, const void *wt, const void *dx);
+hipError_t conv_dgrad_s2_f32_launch(const void *dy, const void *wt, void *dx, int B, int OH, int OW, int N, int H, int W, int C, hipStream_t st);
+
 }  // namespace mdetr

@@ -232,6 +232,11 @@ def conv_bn(x, conv, bn, relu, skip_out=False, relu_token=None, hand_out_token=F
             # the stride-2 3x3 of a stage's first block and its 1x1 / stride-2 projection shortcut (csrc/conv_taps.hip), forward,
             # input gradient (four pixel-parity classes) and weight gradient (csrc/conv_wgrad.hip) by hand
             return conv_taps_ext.conv_strided(x, w, shift, relu=relu, hand_out_token=hand_out_token and relu)
+        elif conv_taps_ext.ENABLED_F32 and not torch.is_autocast_enabled() and not conv_taps_ext._autocast(x) \
+                and conv_taps_ext.supported_f32(x, w, conv.stride, conv.padding, conv.dilation, conv.groups):
+            # the stride-2 3x3 in fp32 (mdetr_conv_taps_f32 / mdetr_conv_dgrad_s2_f32: three-way bf16 split); the weight gradient
+            # stays on the library
+            return conv_taps_ext.conv_strided(x, w, shift, relu=relu, hand_out_token=hand_out_token and relu)
         elif conv3x3_ext.ENABLED and conv3x3_ext.supported(x, w, conv.stride, conv.padding, conv.dilation, conv.groups):
             # stride-1 3x3: implicit GEMM with LDS im2col, shift and ReLU in its epilogue (csrc/conv3x3.hip); forward and
             # input gradient on the kernel, weight gradient with the library

@@ -621,4 +621,7 @@ class PointwiseConv2d(nn.Conv2d):
                 and conv_taps_ext.supported(x, self.weight, self.stride, self.padding, self.dilation, self.groups):
             # 3x3 / stride 2 (the fourth pyramid level, monodetr.py:87-92; the depth predictor's downsample, depth_predictor.py:29-31)
             return conv_taps_ext.conv_strided(x, self.weight, self.bias, relu=False)
+        if conv_taps_ext.ENABLED_F32 and x.dtype == self.weight.dtype and not torch.is_autocast_enabled() and not conv_taps_ext._autocast(x) \
+                and self.padding_mode == "zeros" and conv_taps_ext.supported_f32(x, self.weight, self.stride, self.padding, self.dilation, self.groups):
+            return conv_taps_ext.conv_strided(x, self.weight, self.bias, relu=False)      # the same in fp32 (mdetr_conv_taps_f32)
         return super().forward(x)

@@ -4,6 +4,7 @@ channels_last.  TFLOP/s = 2 B OH OW K K C N / t; `frac_mfma` against the 2.5 PFL
 
     python -m monodetr_amd.tools.convbench [--iters 20] [--only wgrad|strided|stem]
     python -m monodetr_amd.tools.convbench --dtype fp32 [--runs 3]      (the fp32 forms of conv3x3.hip / conv_wgrad.hip against the library: `fp32_rows`)
+    python -m monodetr_amd.tools.convbench --dtype fp32 --only strided  (the fp32 form of conv_taps.hip on the model's stride-2 3x3 sites: `fp32_strided_rows`)
 """
 import argparse
 import json
@@ -66,6 +67,111 @@ def fp32_rows(a, dev, B):
     return res
 
 
+def strided_sites(dev, B, size=(384, 1280)):
+    """(name, C, N, H, W) of every 3x3 / stride-2 / pad-1 convolution of the model, read from the modules during one fp32 training
+    iteration at batch B: a Bottleneck whose conv2 strides sees conv2's input size at its own input (conv1 is 1x1 / stride 1); the
+    pyramid level and the depth predictor's downsample are modules of their own."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", ".."))
+    import bench
+    from monodetr_amd.kernel_families import COMMITTED_SWITCHES
+    from monodetr_amd.monodetr.backbone import Bottleneck
+    step = bench.TrainStep(torch.device(dev), B, "fp32", switches=COMMITTED_SWITCHES["fp32"], graph=False, size=size)
+    is_site = lambda m: isinstance(m, torch.nn.Conv2d) and tuple(m.kernel_size) == (3, 3) and tuple(m.stride) == (2, 2) \
+        and tuple(m.padding) == (1, 1) and m.groups == 1                # noqa: E731
+    sites, hooks, inside = [], [], set()
+
+    def note(name, conv):
+        def hook(mod, args):
+            sites.append((name, conv.in_channels, conv.out_channels, int(args[0].shape[2]), int(args[0].shape[3])))
+        return hook
+    for name, m in step.raw_model.named_modules():
+        if isinstance(m, Bottleneck) and is_site(m.conv2):
+            hooks.append(m.register_forward_pre_hook(note(name + ".conv2", m.conv2)))
+            inside.add(m.conv2)
+    for name, m in step.raw_model.named_modules():
+        if is_site(m) and m not in inside:
+            hooks.append(m.register_forward_pre_hook(note(name, m)))
+    step()
+    for h in hooks:
+        h.remove()
+    del step
+    return sites
+
+
+def fp32_strided_rows(a, dev, B):
+    """--dtype fp32 --only strided: the fp32 form of csrc/conv_taps.hip (mdetr_conv_taps_f32 / its split form + the sum over the splits,
+    mdetr_conv_dgrad_s2_f32) against the library route -- F.conv2d(stride=2) + bias + ReLU forward, convolution_backward(..., (True,
+    False, False)) for dX -- on every 3x3 / stride-2 site of the model (`strided_sites`), by the method of `fp32_rows`.  The pyramid
+    level (no ReLU: GroupNorm follows) is timed with and without the contraction split.  Every class is timed whatever the shape rule of
+    conv_taps_ext says; what the rule routes is reported beside it (`..._routed_to_kernel`)."""
+    import statistics
+    from monodetr_amd import _tune, conv_taps_ext
+    from .gemmbench import graph_time
+    sites = strided_sites(dev, B)
+    conv_taps_ext.ENABLED_F32 = True
+    res, nsets, reps = {"sites": [list(s) for s in sites], "tune": _tune.get("conv_taps_f32_rows", "") + "/" + _tune.get("conv_taps_f32_nb", "")}, 2, max(4, a.iters)
+
+    def row(f, flops):
+        us = sorted(graph_time(f, nsets, reps) for _ in range(a.runs))
+        med = statistics.median(us)
+        return dict(us=round(med, 2), spread_us=[us[0], us[-1]], TFLOPs=round(flops / med / 1e6, 1), frac_six_term_mfma=round(6.0 * flops / (med * 1e-6) / 2.5e15, 4))
+
+    done = {}
+    for name, C, N, H, W in sites:
+        if (C, N, H, W) in done:
+            res["f32_%s" % name] = "same problem as " + done[(C, N, H, W)]
+            continue
+        done[(C, N, H, W)] = name
+        OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        flops = 2.0 * B * OH * OW * 9 * C * N
+        xs = [(torch.randn(B, H, W, C, device=dev) * 0.5).permute(0, 3, 1, 2) for _ in range(nsets)]
+        dys = [torch.randn(B, OH, OW, N, device=dev).permute(0, 3, 1, 2) for _ in range(nsets)]
+        w = (torch.randn(N, 3, 3, C, device=dev) / (3.0 * C ** 0.5)).permute(0, 3, 1, 2)
+        sh = torch.randn(N, device=dev) * 0.5
+        # the measured shape rule (conv_taps_ext._F32_FWD_MAX_C / _F32_DX_MAX_C) is reported per class; both classes are timed all the same
+        res["f32_%s_routed_to_kernel" % name] = dict(supported=bool(conv_taps_ext.supported_f32(xs[0], w)), forward=bool(conv_taps_ext._fwd_on_kernel(xs[0])),
+                                                      dgrad=bool(conv_taps_ext._dx_on_kernel(dys[0], C)))
+        rule = (conv_taps_ext._F32_FWD_MAX_C, conv_taps_ext._F32_DX_MAX_C)
+        conv_taps_ext._F32_FWD_MAX_C = conv_taps_ext._F32_DX_MAX_C = 1 << 30
+        assert conv_taps_ext.supported_f32(xs[0], w), name                 # (dtype, layout and the entry's limits)
+        conv_taps_ext._F32_FWD_MAX_C, conv_taps_ext._F32_DX_MAX_C = rule
+        wo = conv_taps_ext._ohwi(w)                                        # (a view: the weight is channels_last, as the model's are on the GPU)
+        wt = wo.permute(3, 1, 2, 0).contiguous()
+        relu = not name.startswith("input_proj")
+        ks = conv_taps_ext._split_count(B, OH, OW, N, C, 3, relu)
+        res["f32_fwd_%s_kernel" % name] = dict(row(lambda i: conv_taps_ext._forward(xs[i], wo, sh, relu), flops), ksplit=ks)
+        if ks:
+            with _no_split():
+                res["f32_fwd_%s_kernel_unsplit" % name] = row(lambda i: conv_taps_ext._forward(xs[i], wo, sh, relu), flops)
+        lib_fwd = (lambda i: F.relu_(F.conv2d(xs[i], w, sh, stride=2, padding=1))) if relu else (lambda i: F.conv2d(xs[i], w, sh, stride=2, padding=1))
+        res["f32_fwd_%s_library" % name] = row(lib_fwd, flops)
+        res["f32_dgrad_%s_kernel" % name] = row(lambda i: conv_taps_ext._input_gradient(dys[i], wo, H, W, wt), flops)
+        # as the routed autograd node runs it: fp32 weights carry no [C, 3, 3, N] copy (`_mdetr_ihwo` is made by the bf16 fold kernel only),
+        # so every backward pass transposes the weight first
+        res["f32_dgrad_%s_kernel_with_weight_transpose" % name] = row(lambda i: conv_taps_ext._input_gradient(dys[i], wo, H, W), flops)
+        res["f32_dgrad_%s_library" % name] = row(lambda i: torch.ops.aten.convolution_backward(
+            dys[i], xs[i], w, None, (2, 2), (1, 1), (1, 1), False, (0, 0), 1, (True, False, False)), flops)
+    return res
+
+
+class _no_split:
+    """MDETR_TUNE conv_taps_split=0 for the duration of a block (the unsplit forward of a site the route would split)."""
+
+    def __enter__(self):
+        import os
+        self.old = os.environ.get("MDETR_TUNE")
+        os.environ["MDETR_TUNE"] = ",".join(x for x in (self.old, "conv_taps_split=0") if x)
+
+    def __exit__(self, *exc):
+        import os
+        if self.old is None:
+            os.environ.pop("MDETR_TUNE", None)
+        else:
+            os.environ["MDETR_TUNE"] = self.old
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -77,7 +183,7 @@ def main():
     dev, B = "cuda", a.batch
     from monodetr_amd import conv3x3_ext, conv_taps_ext, conv_wgrad_ext
     if a.dtype == "fp32":
-        print(json.dumps(fp32_rows(a, dev, B)))
+        print(json.dumps(fp32_strided_rows(a, dev, B) if a.only == "strided" else fp32_rows(a, dev, B)))
         return
     conv_wgrad_ext.ENABLED = True
     res = {}
