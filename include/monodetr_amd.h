@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MDETR_ABI_VERSION 17
+#define MDETR_ABI_VERSION 18
 
 /* element types of the floating-point tensors */
 #define MDETR_F32 0
@@ -423,10 +423,19 @@ int mdetr_tgemm_f32_masked(const void *a, const void *w, const void *res, const 
  *   c      [M, N] (row stride ldc), c_dtype MDETR_F32 or MDETR_BF16 (one rounding at the store).
  * Any shape: ragged edges are guarded element-wise; rows whose stride and base allow it are read with 16-byte loads.  Deterministic
  * (fixed summation order, no atomics).
+ *
+ * MDETR_SGEMM_SPLIT (ABI 18), OR-ed into `mode` of both entries below: the same products through the three-way bf16 split of
+ * csrc/mdetr_split.h on the bf16 matrix instruction -- every fp32 operand element as hi + mid + lo bf16 parts, six terms per k-step
+ * into one fp32 accumulator (three where one operand is bf16).  Products are fp32-exact up to the dropped terms, <= 2^-25 |a||b| per
+ * product; accumulation is fp32; same epilogue, shapes, determinism.  An infinite fp32 operand gives NaN (x - bf16(x)).  WITHOUT the
+ * flag nothing changes: the call computes the exact k-ordered fmaf chain described above.  The workspace size of a TN group depends
+ * on the flag: ask mdetr_sgemm_workspace_bytes with the mode you launch.  (MDETR_TUNE key sgemm_split=0|1 overrides the flag in both
+ * entries: A/B runs and tests.)
  */
 #define MDETR_SGEMM_NT 0
 #define MDETR_SGEMM_NN 1
 #define MDETR_SGEMM_TN 2
+#define MDETR_SGEMM_SPLIT 16 /* OR-ed into mode: the three-way bf16 split form (below) */
 #define MDETR_SGEMM_MAX_PROBLEMS 10
 #define MDETR_SGEMM_MAX_TERMS 5
 typedef struct {

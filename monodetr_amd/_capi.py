@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MDETR_LIB_PATH") or os.path.join(_HERE, "libmonodetr_
 
 MDETR_F32, MDETR_F64, MDETR_BF16 = 0, 1, 2
 MDETR_E_UNSUPPORTED = -4
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _c_int, _c_vp = ctypes.c_int, ctypes.c_void_p
 

@@ -1,4 +1,5 @@
-// monodetr_amd/csrc/sgemm.hip -- grouped fp32 products on the f32-input matrix instruction (v_mfma_f32_32x32x2_f32).
+// monodetr_amd/csrc/sgemm.hip -- grouped fp32 products: exact on the f32-input matrix instruction (v_mfma_f32_32x32x2_f32), or through the
+// three-way bf16 split on the bf16 one (v_mfma_f32_32x32x16_bf16; MDETR_SGEMM_SPLIT).
 //
 // The prediction heads of MonoDETR (lib/models/monodetr/monodetr.py:222-262: class / box / size / angle / depth MLPs on the
 // [B x 550, 256] output of every decoder level) stay in fp32 behind the bf16 body.  They are 18 small products per level and direction
@@ -6,10 +7,9 @@
 // launches, 0.96 ms of the round-5 step, most of it fill and drain).  This file runs them as GROUPS: one launch covers every product
 // of a dependency level (the five first layers; the second layers; ...), a workgroup looks its tile up in the group's table.
 //
-// Arithmetic: `mfma_f32` is exact fp32 (the k-ordered fmaf chain), at the fp32 vector rate -- 1/16 of the bf16 instruction, which is
-// still 155 TFLOP/s; the heads are 27 GFLOP per step.  No operand is rounded to a narrower type anywhere (bf16 OPERANDS -- the
-// decoder output of the bf16 body -- are widened on load, which is exact).
-//
+// THE EXACT FORM (the unflagged call).  `mfma_f32` is exact fp32 (the k-ordered fmaf chain), at the fp32 vector rate -- 1/16 of the
+// bf16 instruction, which is still 155 TFLOP/s; the heads are 27 GFLOP per step.  No operand is rounded to a narrower type anywhere
+// (bf16 OPERANDS -- the decoder output of the bf16 body -- are widened on load, which is exact).
 // Layout of a product C[M, N] = sum_t A_t op(B_t):
 //   NT / NN: a 256-thread workgroup owns a 64 x 64 tile, its four waves a 32 x 32 quadrant each; the contraction runs in slabs of 32
 //            through LDS (double-buffered; the next slab's global loads fly during the current slab's 16 matrix instructions).  An
@@ -21,15 +21,29 @@
 //            so lanes load straight from global memory, no LDS.  Lane (i, h) loads the column PAIRS A[t + h][m0 + 2 i, + 1] and
 //            B[t + h][n0 + 2 i, + 1] (one 8-byte load each) and issues four instructions on them -- even / odd columns of either
 //            operand, a 64 x 64 tile per wave in four accumulators whose rows / columns interleave.  (One value per load and
-//            instruction, the first version, was bound by the L2 at 106 us for a level's weight gradients.)  A 1024-thread workgroup
-//            owns the tile; its sixteen waves take a sixteenth of the rows each and are summed pairwise through LDS in a fixed tree
-//            (deterministic); the column sums of A (the bias gradient) ride on the A operand's registers.
+//            instruction, the first version, was bound by the L2 at 106 us for a level's weight gradients.)  A 256-thread workgroup
+//            (kTnWaves = 4) owns the tile and one part of the contraction (grid.y); its four waves take a quarter of that part's
+//            rows each and are summed pairwise through LDS in a fixed tree (deterministic); the column sums of A (the bias
+//            gradient) ride on the A operand's registers.
+//
+// THE SPLIT FORM (MDETR_SGEMM_SPLIT OR-ed into the mode; sgemm_split_kernel below, sibling kernels -- the exact kernels carry no flag
+// for it).  An fp32 operand element is split once, on its way from the staging registers into LDS, as hi + mid + lo bf16
+// (mdetr_split.h); LDS holds bf16 planes; a k-step of 16 issues lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi (small ones first)
+// into ONE fp32 accumulator -- 6/16 of the f32-input instruction's time.  A bf16 operand is its own hi plane and has no other:
+// three terms (one if both are bf16).  Products stay fp32-exact: the dropped mid.lo + lo.mid + lo.lo sum to <= 2^-25 |a||b| per
+// product.  x - bf16(x) is NaN for +-inf: an INFINITE fp32 operand gives NaN in this form (as in tgemm / twgrad / conv3x3's).
+// All three modes stage through LDS (the bf16 instruction contracts 16 rows per issue, so TN's operands are staged row-major and
+// read with the transposing LDS read, twgrad32_kernel's structure); tiles are 64 x 64, or 32 x 64 for NT / NN groups of few tiles;
+// TN keeps grid = (tiles, parts), the partials and sgemm_tn_reduce.  Group table, problem / term lookup, every epilogue, ragged
+// shapes and alignment fallbacks are the exact form's code.  See the section comment further down.
 // Ragged shapes are guarded per element; vector loads are used where the stride and base pointer allow them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <mdetr_wave.h>
 
+#include "mdetr_split.h"
+#include "mdetr_tune.h"
 #include "msda.h"        // ProfileScope
 #include "sgemm.h"
 
@@ -596,6 +610,294 @@ void sgemm_tn_kernel(const Args a)
     if (tn == 0 && mm < PM) part[static_cast<int64_t>(PM) * PN + mm] = sum;
 }
 
+// ---- the split form (MDETR_SGEMM_SPLIT) --------------------------------------------------------------------------------------------
+// One kernel for the three modes: a 256-thread workgroup owns a 64 x 64 tile (four waves, a 32 x 32 quadrant each) and walks the
+// contraction in slabs of 32 through LDS.  What differs between the modes is how an operand lies in memory, i.e. its LDS image:
+//   KC  the contraction index is contiguous (A of NT / NN, B of NT): planes [64 rows][32 + 8] bf16, fragment = one ds_read_b128;
+//   KR  the contraction index is the ROW (B of NN, both operands of TN): planes [32 k][64 + 8] bf16, fragment = tr_fragment.
+// Staging maps, guards and the three-slab register ring are the exact form's (raw4 / decode4: no load behind a per-lane branch).
+constexpr int kPitchC = kSlab + 8, kPitchR = kTile + 32;           // bf16 per LDS row (16- / 8-byte aligned; KR: twgrad.hip's padding)
+constexpr int kPlaneR = kSlab * kPitchR;
+constexpr int plane_c(int rows) { return rows * kPitchC; }
+static_assert((kPitchC * 2) % 16 == 0 && (kPitchR * 2) % 8 == 0 && (plane_c(32) * 2) % 16 == 0 && (kPlaneR * 2) % 16 == 0, "aligned fragment reads");
+
+// fragment of a 32-column block of a KR plane: lane l -> column l & 31, contraction rows 8 (l >> 5) .. + 7 of the k-step whose first
+// row is `rows` (twgrad.hip's: two transposing reads; lane s of a 16-lane group points at row s >> 2, columns 4 (s & 3))
+__device__ __forceinline__ bf16x8 tr_fragment(const __bf16 *rows, int pitch, int lane)
+{
+    const int s = lane & 15, grp = lane >> 4;
+    const __bf16 *p = rows + (8 * (grp >> 1) + (s >> 2)) * pitch + 16 * (grp & 1) + 4 * (s & 3);
+    const bf16x4 lo = lds_read_tr4(p), hi = lds_read_tr4(p + 4 * pitch);
+    bf16x8 f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { f[i] = lo[i]; f[4 + i] = hi[i]; }
+    return f;
+}
+
+struct SplitOp {                       // one operand of a term as the workgroup stages it (uniform)
+    const void *base;
+    int64_t ld;
+    int lim, t0;                       // KC: rows the operand has / the tile's first row; KR: columns / first column
+    bool vec;                          // rows may be read with vector loads
+};
+
+// The thread's piece p (four consecutive elements) of the slab at k0.  KC: row t0 + r + 32 p, k = k0 + q .. + 3 (r = tid / 8,
+// q = 4 (tid % 8)); KR: k = k0 + r + 16 p, columns t0 + q .. + 3 (r = tid / 16, q = 4 (tid % 16)).
+// FULL (a compile-time property of the call, decided per term from uniform values): every piece of every slab of the call exists
+// and may be read with one vector load -- KC: the call covers whole slabs (rows beyond the operand read its last row: results
+// nobody stores); KR: whole slabs and the tile's 64 columns inside the operand.  Otherwise four guarded element loads per piece.
+// Either way the loads sit in straight-line code: element type and form are template parameters, not branches.
+template <bool KR, bool FULL> __device__ __forceinline__ int op_valid(const SplitOp &o, int r, int q, int p, int k0, int k_end)
+{
+    if (FULL) return 4;
+    if (KR) return k0 + r + 16 * p < k_end ? clamp04(o.lim - (o.t0 + q)) : 0;
+    return o.t0 + r + 32 * p < o.lim ? clamp04(k_end - (k0 + q)) : 0;
+}
+template <bool KR, bool FULL> __device__ __forceinline__ int64_t op_off(const SplitOp &o, int r, int q, int p, int k0)
+{
+    if (KR) return static_cast<int64_t>(k0 + r + 16 * p) * o.ld + o.t0 + q;
+    return static_cast<int64_t>(FULL ? min(o.t0 + r + 32 * p, o.lim - 1) : o.t0 + r + 32 * p) * o.ld + k0 + q;
+}
+
+// four staged values -> LDS: an fp32 operand is split here, once per element, into its hi / mid / lo planes; a bf16 operand is its
+// own hi plane (the conversion back is exact) and has no other
+template <bool BF> __device__ __forceinline__ void put_planes(__bf16 *plane0, int plane, int dst, const f32x4 &v)
+{
+    const float x[4] = {v.x, v.y, v.z, v.w};
+    bf16x4 h, m, l;
+    if (BF) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) h[i] = static_cast<__bf16>(x[i]);
+        *reinterpret_cast<bf16x4 *>(plane0 + dst) = h;
+    } else {
+        split4(x, h, m, l);
+        *reinterpret_cast<bf16x4 *>(plane0 + dst) = h;
+        *reinterpret_cast<bf16x4 *>(plane0 + plane + dst) = m;
+        *reinterpret_cast<bf16x4 *>(plane0 + 2 * plane + dst) = l;
+    }
+}
+
+// Geometry of a split kernel.  TM: rows of the tile.  64: four waves, a 32 x 32 quadrant each, both k-steps of a slab.  32 (NT / NN,
+// for groups of few tiles -- twice the workgroups): the waves (wn, kh) own the 32 x 32 column half wn and the k-step kh of every
+// slab; the two k-halves are added through LDS at the end, kh = 0 first.
+template <int MODE, int TM> struct SplitGeo {
+    static constexpr bool AKR = MODE == MDETR_SGEMM_TN, BKR = MODE != MDETR_SGEMM_NT;
+    static constexpr int PA = AKR ? kPlaneR : plane_c(TM), PB = BKR ? kPlaneR : plane_c(kTile);
+    static constexpr int NPA = AKR ? 2 : TM / 32;                  // pieces of A per thread and slab (B: always 2)
+    static constexpr int KS = TM == 64 ? 2 : 1;                    // k-steps of a slab per wave
+    static_assert(TM == 64 || (TM == 32 && !AKR), "32-row tiles: NT / NN");
+};
+
+// the matrix instructions of one staged slab on this wave's block: per k-step of 16 the six terms lo.hi, hi.lo, mid.mid, mid.hi,
+// hi.mid, hi.hi (A part . B part, small ones first) into one accumulator; a bf16 operand has only its hi part (three terms, or one).
+// `want_cs`: the column sums of A (TN) as products with ones, lo, mid, hi.
+template <typename G, bool ABF, bool BBF>
+__device__ __forceinline__ void split_products(const __bf16 *Ab, const __bf16 *Bb, int wm, int wn, int kh, int lane, f32x16 &acc, f32x16 &accb,
+                                               bool want_cs)
+{
+    constexpr int NA = ABF ? 1 : 3, NB = BBF ? 1 : 3;
+    constexpr int term_a[6] = {2, 0, 1, 1, 0, 0}, term_b[6] = {0, 2, 1, 0, 1, 0};
+    const int li = lane & 31, lh = lane >> 5;
+    bf16x8 ones;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ones[i] = static_cast<__bf16>(1.0f);
+#pragma unroll
+    for (int j = 0; j < G::KS; ++j) {
+        const int ks = G::KS == 2 ? j : kh;                        // (a 32-row tile: this wave's k-step of the slab)
+        bf16x8 af[NA], bf[NB];
+#pragma unroll
+        for (int p = 0; p < NA; ++p) {
+            if (G::AKR) af[p] = tr_fragment(Ab + p * G::PA + ks * 16 * kPitchR + wm * 32, kPitchR, lane);
+            else af[p] = *reinterpret_cast<const bf16x8 *>(Ab + p * G::PA + (wm * 32 + li) * kPitchC + 16 * ks + 8 * lh);
+        }
+#pragma unroll
+        for (int p = 0; p < NB; ++p) {
+            if (G::BKR) bf[p] = tr_fragment(Bb + p * G::PB + ks * 16 * kPitchR + wn * 32, kPitchR, lane);
+            else bf[p] = *reinterpret_cast<const bf16x8 *>(Bb + p * G::PB + (wn * 32 + li) * kPitchC + 16 * ks + 8 * lh);
+        }
+#pragma unroll
+        for (int t = 0; t < 6; ++t)
+            if (term_a[t] < NA && term_b[t] < NB) acc = mfma_bf16(af[term_a[t] < NA ? term_a[t] : 0], bf[term_b[t] < NB ? term_b[t] : 0], acc);
+        if (want_cs) {                                             // (wave-uniform)
+#pragma unroll
+            for (int p = NA - 1; p >= 0; --p) accb = mfma_bf16(af[p], ones, accb);
+        }
+    }
+}
+
+struct SplitCtx {
+    SplitOp A, B;
+    int ar, aq, br, bq;                // this thread's staging coordinates in either operand's slab
+    int wm, wn, kh, lane;
+    bool want_cs;
+};
+
+// One term over the contraction rows [k_begin, k_end): THREE slabs in flight in registers (as term_fast), every load guarded or
+// FULL per operand.  ONE LDS image of a slab (measured against two: half the LDS, three workgroups per CU instead of two, is worth
+// more than the barrier it costs -- between a slab's last fragment read and the next slab's planes).
+template <typename G, bool ABF, bool BBF, bool AFULL, bool BFULL>
+__device__ __forceinline__ void split_term(const SplitCtx &c, int k_begin, int k_end, __bf16 *Ap, __bf16 *Bp, f32x16 &acc, f32x16 &accb)
+{
+    constexpr bool AKR = G::AKR, BKR = G::BKR;
+    const int slabs = (k_end - k_begin + kSlab - 1) / kSlab;
+    if (slabs <= 0) return;                                        // (uniform: a TN part beyond the contraction)
+    u32x4 ra[3][2], rb[3][2];
+    auto load = [&](int s, u32x4 (&xa)[2], u32x4 (&xb)[2]) {
+        const int k0 = k_begin + min(s, slabs - 1) * kSlab;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            if (p < G::NPA) xa[p] = raw4(c.A.base, ABF, op_off<AKR, AFULL>(c.A, c.ar, c.aq, p, k0), op_valid<AKR, AFULL>(c.A, c.ar, c.aq, p, k0, k_end), AFULL);
+            xb[p] = raw4(c.B.base, BBF, op_off<BKR, BFULL>(c.B, c.br, c.bq, p, k0), op_valid<BKR, BFULL>(c.B, c.br, c.bq, p, k0, k_end), BFULL);
+        }
+    };
+    auto store = [&](int s, const u32x4 (&xa)[2], const u32x4 (&xb)[2]) {
+        const int k0 = k_begin + s * kSlab;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int da = AKR ? (c.ar + 16 * p) * kPitchR + c.aq : (c.ar + 32 * p) * kPitchC + c.aq;
+            const int db = BKR ? (c.br + 16 * p) * kPitchR + c.bq : (c.br + 32 * p) * kPitchC + c.bq;
+            if (p < G::NPA) put_planes<ABF>(Ap, G::PA, da, decode4(xa[p], ABF, op_valid<AKR, AFULL>(c.A, c.ar, c.aq, p, k0, k_end), AFULL));
+            put_planes<BBF>(Bp, G::PB, db, decode4(xb[p], BBF, op_valid<BKR, BFULL>(c.B, c.br, c.bq, p, k0, k_end), BFULL));
+        }
+    };
+    if (!AFULL && !BFULL && slabs <= 2) {                          // (uniform) a ragged rest, the short contractions of the narrow heads: load, wait, use
+        for (int s2 = 0; s2 < slabs; ++s2) {
+            load(s2, ra[0], rb[0]);
+            store(s2, ra[0], rb[0]);
+            __syncthreads();
+            split_products<G, ABF, BBF>(Ap, Bp, c.wm, c.wn, c.kh, c.lane, acc, accb, c.want_cs);
+            __syncthreads();
+        }
+        return;
+    }
+    // Every load of the pipeline is issued UNCONDITIONALLY (beyond the last slab: the last slab again, from the cache, never
+    // stored): a load behind even a uniform branch leaves the number of loads in flight unknown at the join, and the wait before
+    // each LDS store then becomes a wait for all of them -- load, wait, use, one memory latency per slab.
+    load(0, ra[0], rb[0]);
+    load(1, ra[1], rb[1]);
+    load(2, ra[2], rb[2]);
+    store(0, ra[0], rb[0]);
+    __syncthreads();
+    // slab s2 sits in LDS; ring slot s2 % 3 is free (its slab is in LDS), slot (s2 + 1) % 3 goes to LDS next
+#define MDETR_SGEMM_SPLIT_STEP(FREE, NEXT)                                                                             \
+    {                                                                                                                  \
+        load(s2 + 3, ra[FREE], rb[FREE]);                                                                              \
+        split_products<G, ABF, BBF>(Ap, Bp, c.wm, c.wn, c.kh, c.lane, acc, accb, c.want_cs);                           \
+        __syncthreads();                                                                                               \
+        if (s2 + 1 < slabs) store(s2 + 1, ra[NEXT], rb[NEXT]);                                                         \
+        __syncthreads();                                                                                               \
+        if (++s2 >= slabs) break;                                                                                      \
+    }
+    for (int s2 = 0;;) {
+        MDETR_SGEMM_SPLIT_STEP(0, 1)
+        MDETR_SGEMM_SPLIT_STEP(1, 2)
+        MDETR_SGEMM_SPLIT_STEP(2, 0)
+    }
+#undef MDETR_SGEMM_SPLIT_STEP
+}
+
+// a term over [k_begin, k_end): its whole slabs in the FULL form of either operand where that operand allows it, then the ragged
+// rest (at most one slab) guarded; the sixteen combinations of element type and form are compiled once each (a loop of two passes)
+template <typename G>
+__device__ __forceinline__ void split_term_dispatch(const SplitCtx &c, int abf, int bbf, int k_begin, int k_end, __bf16 *Ap, __bf16 *Bp,
+                                                    f32x16 &acc, f32x16 &accb)
+{
+    const int k_mid = k_begin + (k_end - k_begin) / kSlab * kSlab;
+    const bool afull = c.A.vec && (!G::AKR || c.A.t0 + kTile <= c.A.lim), bfull = c.B.vec && (!G::BKR || c.B.t0 + kTile <= c.B.lim);
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        const int kb = pass == 0 ? k_begin : k_mid, ke = pass == 0 ? k_mid : k_end;
+        if (ke <= kb) continue;
+        const int v = (abf ? 8 : 0) | (bbf ? 4 : 0) | (pass == 0 && afull ? 2 : 0) | (pass == 0 && bfull ? 1 : 0);
+#define MDETR_SGEMM_SPLIT_CASE(V)                                                                                                              \
+        case V: split_term<G, ((V) & 8) != 0, ((V) & 4) != 0, ((V) & 2) != 0, ((V) & 1) != 0>(c, kb, ke, Ap, Bp, acc, accb); break;
+        switch (v) {
+            MDETR_SGEMM_SPLIT_CASE(0) MDETR_SGEMM_SPLIT_CASE(1) MDETR_SGEMM_SPLIT_CASE(2) MDETR_SGEMM_SPLIT_CASE(3)
+            MDETR_SGEMM_SPLIT_CASE(4) MDETR_SGEMM_SPLIT_CASE(5) MDETR_SGEMM_SPLIT_CASE(6) MDETR_SGEMM_SPLIT_CASE(7)
+            MDETR_SGEMM_SPLIT_CASE(8) MDETR_SGEMM_SPLIT_CASE(9) MDETR_SGEMM_SPLIT_CASE(10) MDETR_SGEMM_SPLIT_CASE(11)
+            MDETR_SGEMM_SPLIT_CASE(12) MDETR_SGEMM_SPLIT_CASE(13) MDETR_SGEMM_SPLIT_CASE(14) MDETR_SGEMM_SPLIT_CASE(15)
+        }
+#undef MDETR_SGEMM_SPLIT_CASE
+    }
+}
+
+// MODE: MDETR_SGEMM_NT / NN / TN.  NT / NN: grid = tiles, all terms of the problem into one accumulator, then the exact form's
+// epilogue.  TN: grid = (tiles, split) as sgemm_tn_kernel -- workgroup (tile, s) contracts rows [s, s + 1) * chunk; its four waves
+// own quadrants of the tile (the operands pass through LDS), so there is nothing to sum inside the workgroup; the partials and
+// sgemm_tn_reduce are the exact form's, the column sums of A are three more matrix instructions per k-step on the waves that hold
+// the tile's first column block.  Fixed order, no atomics.
+template <int MODE, int TM>
+__global__ __launch_bounds__(256, 3)                               // three workgroups per CU (<= 168 registers; LDS allows four)
+void sgemm_split_kernel(const Args a)
+{
+    typedef SplitGeo<MODE, TM> G;
+    constexpr bool AKR = G::AKR, BKR = G::BKR;
+    __shared__ __attribute__((aligned(16))) __bf16 Ap[3 * G::PA];   // [plane hi / mid / lo]
+    __shared__ __attribute__((aligned(16))) __bf16 Bp[3 * G::PB];
+    __shared__ __attribute__((aligned(16))) Args largs;
+    static_assert(sizeof(Bp) >= 2 * 16 * 64 * sizeof(float), "the k-halves of a 32-row tile meet in the B planes");
+    const int tile = blockIdx.x;
+    const Prob &P = stage_args(a, &largs, tile);
+    const Term *terms = &largs.t[wave_uniform(P.term0)];
+    const int tiles_n = wave_uniform(P.tiles_n), lt = tile - wave_uniform(P.tile0);
+    const int PM = wave_uniform(P.M), PN = wave_uniform(P.N), tm = lt / tiles_n, tn = lt - tm * tiles_n;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, lh = lane >> 5;
+    SplitCtx c;
+    c.ar = AKR ? tid >> 4 : tid >> 3; c.aq = AKR ? (tid & 15) << 2 : (tid & 7) << 2;
+    c.br = BKR ? tid >> 4 : tid >> 3; c.bq = BKR ? (tid & 15) << 2 : (tid & 7) << 2;
+    c.wm = TM == 64 ? wave >> 1 : 0; c.kh = TM == 64 ? 0 : wave >> 1; c.wn = wave & 1; c.lane = lane;
+    c.want_cs = MODE == MDETR_SGEMM_TN && tn == 0 && c.wn == 0;
+    c.A.lim = PM; c.A.t0 = tm * TM; c.B.lim = PN; c.B.t0 = tn * kTile;
+
+    f32x16 acc, accb;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = accb[r] = 0.f;
+
+    const int nterm = MODE == MDETR_SGEMM_TN ? 1 : wave_uniform(P.nterm), split = wave_uniform(largs.split);
+    for (int t = 0; t < nterm; ++t) {
+        const Term T = uniform_term(terms[t]);
+        c.A.base = T.a; c.A.ld = T.lda; c.A.vec = vec_ok(T.a, T.lda, T.a_bf16);
+        c.B.base = T.b; c.B.ld = T.ldb; c.B.vec = vec_ok(T.b, T.ldb, T.b_bf16);
+        int k_begin = 0, k_end = T.K;
+        if (MODE == MDETR_SGEMM_TN) {                              // this workgroup's part of the contraction, in whole slabs
+            const int chunk = ((T.K + split * kSlab - 1) / (split * kSlab)) * kSlab;
+            k_begin = min(T.K, static_cast<int>(blockIdx.y) * chunk);
+            k_end = min(T.K, k_begin + chunk);
+        }
+        split_term_dispatch<G>(c, T.a_bf16, T.b_bf16, k_begin, k_end, Ap, Bp, acc, accb);
+    }
+    if (TM == 32) {                                                // k-step 1's waves hand their block to k-step 0's (every slab loop ends with a barrier)
+        float *red = reinterpret_cast<float *>(&Bp[0]) + c.wn * 16 * 64;
+        if (c.kh == 1) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) red[r * 64 + lane] = acc[r];
+        }
+        __syncthreads();
+        if (c.kh == 1) return;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] += red[r * 64 + lane];
+    }
+    const int row0 = tm * TM + c.wm * 32, col = tn * kTile + c.wn * 32 + li;
+    if (MODE != MDETR_SGEMM_TN || split == 1) {
+        epilogue_tile(P, row0, 1, col, lh, acc);
+        if (MODE == MDETR_SGEMM_TN && P.colsum && c.want_cs && li == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                if (row < PM) as_global_rw<float>(P.colsum)[row] = accb[r];
+            }
+        }
+        return;
+    }
+    MDETR_GLOBAL float *part = as_global_rw<float>(largs.ws) + static_cast<int64_t>(blockIdx.y) * largs.flat + P.foff;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (row < PM && col < PN) part[static_cast<int64_t>(row) * PN + col] = acc[r];
+        if (c.want_cs && li == 0 && row < PM) part[static_cast<int64_t>(PM) * PN + row] = accb[r];
+    }
+}
+
 // C = the sum of the `split` partials, in order; one thread per element of the flat result (M x N values + M column sums per problem)
 __global__ __launch_bounds__(256)
 void sgemm_tn_reduce(const Args a)
@@ -628,17 +930,45 @@ void sgemm_tn_reduce(const Args a)
 }
 
 // how many parts the contraction of a TN group is cut into: enough workgroups to fill the chip, parts of >= 64 rows per wave
-int tn_split(const mdetr_sgemm_problem *p, int nprob)
+int tn_split(const mdetr_sgemm_problem *p, int nprob, int target = 768)
 {
     int tiles = 0, kmin = 1 << 30;
     for (int i = 0; i < nprob; ++i) {
         tiles += ((p[i].m + kTnTile - 1) / kTnTile) * ((p[i].n + kTnTile - 1) / kTnTile);
         kmin = p[i].term[0].k < kmin ? p[i].term[0].k : kmin;
     }
-    int s = (768 + tiles - 1) / tiles;
+    int s = (target + tiles - 1) / tiles;
     const int by_rows = kmin / (64 * kTnWaves);
     s = s < by_rows ? s : by_rows;
     return s < 1 ? 1 : (s > kTnMaxSplit ? kTnMaxSplit : s);
+}
+
+// ... in the split form: a workgroup per tile and part, parts of >= 128 rows (four slabs); the count that fills `places` without
+// starting another round (tools/rounds.py)
+constexpr int kSplitPlaces = 768;                                  // three workgroups per CU
+int tn_split_form(const mdetr_sgemm_problem *p, int nprob)
+{
+    int tiles = 0, kmin = 1 << 30;
+    for (int i = 0; i < nprob; ++i) {
+        tiles += ((p[i].m + kTile - 1) / kTile) * ((p[i].n + kTile - 1) / kTile);
+        kmin = p[i].term[0].k < kmin ? p[i].term[0].k : kmin;
+    }
+    int places = tune_int("sgemm_split_tn_wgs", 0);                // tests and A/B runs
+    if (places < 1 || places > 16384) places = kSplitPlaces;
+    int s = places / tiles;
+    const int by_rows = kmin / 128;
+    s = s < by_rows ? s : by_rows;
+    return s < 1 ? 1 : (s > kTnMaxSplit ? kTnMaxSplit : s);
+}
+
+// rows of the split form's tile in NT / NN: 32 for a group that would leave places empty with 64
+int split_tile_rows(const mdetr_sgemm_problem *p, int nprob)
+{
+    const int forced = tune_int("sgemm_split_tm", 0);              // tests and A/B runs
+    if (forced == 32 || forced == 64) return forced;
+    int tiles = 0;
+    for (int i = 0; i < nprob; ++i) tiles += ((p[i].m + kTile - 1) / kTile) * ((p[i].n + kTile - 1) / kTile);
+    return tiles <= kSplitPlaces / 2 ? 32 : 64;                    // (<= 384 tiles of 64 rows: at most one round of 32-row tiles)
 }
 
 int64_t tn_flat(const mdetr_sgemm_problem *p, int nprob)
@@ -650,10 +980,18 @@ int64_t tn_flat(const mdetr_sgemm_problem *p, int nprob)
 
 bool dtype_ok(int d) { return d == MDETR_F32 || d == MDETR_BF16; }
 
+// the split form: the caller's MDETR_SGEMM_SPLIT flag, unless MDETR_TUNE's sgemm_split=0|1 says otherwise (A/B runs and tests)
+bool want_split(int mode)
+{
+    const int forced = tune_int("sgemm_split", -1);
+    return forced == 0 ? false : (forced == 1 ? true : (mode & MDETR_SGEMM_SPLIT) != 0);
+}
+
 }  // namespace
 
 const char *sgemm_check(int mode, const mdetr_sgemm_problem *p, int nprob)
 {
+    mode &= ~MDETR_SGEMM_SPLIT;
     if (mode != MDETR_SGEMM_NT && mode != MDETR_SGEMM_NN && mode != MDETR_SGEMM_TN) return "unknown mode";
     if (!p || nprob <= 0 || nprob > MDETR_SGEMM_MAX_PROBLEMS) return "1 .. MDETR_SGEMM_MAX_PROBLEMS problems per group";
     int terms = 0;
@@ -681,19 +1019,24 @@ const char *sgemm_check(int mode, const mdetr_sgemm_problem *p, int nprob)
 
 int64_t sgemm_workspace_bytes(int mode, const mdetr_sgemm_problem *p, int nprob)
 {
+    const bool split_form = want_split(mode);
+    mode &= ~MDETR_SGEMM_SPLIT;
     if (mode != MDETR_SGEMM_TN) return 0;
-    const int split = tn_split(p, nprob);
+    const int split = split_form ? tn_split_form(p, nprob) : tn_split(p, nprob);
     return split > 1 ? static_cast<int64_t>(split) * tn_flat(p, nprob) * 4 : 0;
 }
 
 hipError_t sgemm_launch(int mode, const mdetr_sgemm_problem *p, int nprob, void *workspace, hipStream_t st)
 {
+    const bool split_form = want_split(mode);
+    mode &= ~MDETR_SGEMM_SPLIT;
     Args a;
     a.split = 1; a.flat = 0; a.ws = nullptr;
     int tiles = 0, terms = 0;
     int64_t foff = 0;
     double flop = 0.0, bytes = 0.0;
     const int tsz = mode == MDETR_SGEMM_TN ? kTnTile : kTile;
+    const int tsz_m = split_form && mode != MDETR_SGEMM_TN ? split_tile_rows(p, nprob) : tsz;
     for (int i = 0; i < nprob; ++i) {
         const mdetr_sgemm_problem &q = p[i];
         Prob &P = a.p[i];
@@ -704,7 +1047,7 @@ hipError_t sgemm_launch(int mode, const mdetr_sgemm_problem *p, int nprob, void 
         P.flags = (q.c_dtype == MDETR_BF16 ? kFlagCBf16 : 0) | (q.res && q.res_dtype == MDETR_BF16 ? kFlagResBf16 : 0);
         P.foff = static_cast<int>(foff); P.pad_ = 0;
         foff += static_cast<int64_t>(q.m) * q.n + q.m;
-        tiles += ((q.m + tsz - 1) / tsz) * P.tiles_n;
+        tiles += ((q.m + tsz_m - 1) / tsz_m) * P.tiles_n;
         bytes += static_cast<double>(q.m) * q.n * (q.c_dtype == MDETR_BF16 ? 2.0 : 4.0) * (1.0 + (q.res ? 1.0 : 0.0)) + (q.mask ? 4.0 * q.m * q.n : 0.0);
         for (int t = 0; t < q.nterm; ++t) {
             const mdetr_sgemm_term &x = q.term[t];
@@ -717,13 +1060,20 @@ hipError_t sgemm_launch(int mode, const mdetr_sgemm_problem *p, int nprob, void 
     }
     a.nprob = nprob;
     ProfileScope prof(21, tiles, st, flop / 1e6, bytes / 1e3);
+#define MDETR_SGEMM_SPLIT_LAUNCH(MODE, TM, GRID) hipLaunchKernelGGL((sgemm_split_kernel<MODE, TM>), GRID, dim3(256), 0, st, a);
     if (mode == MDETR_SGEMM_TN) {
-        a.split = tn_split(p, nprob);
+        a.split = split_form ? tn_split_form(p, nprob) : tn_split(p, nprob);
         a.flat = static_cast<int>(tn_flat(p, nprob));
         a.ws = static_cast<float *>(workspace);
-        hipLaunchKernelGGL(sgemm_tn_kernel, dim3(tiles, a.split), dim3(64 * kTnWaves), 0, st, a);
+        if (split_form) MDETR_SGEMM_SPLIT_LAUNCH(MDETR_SGEMM_TN, 64, dim3(tiles, a.split))
+        else hipLaunchKernelGGL(sgemm_tn_kernel, dim3(tiles, a.split), dim3(64 * kTnWaves), 0, st, a);
         if (a.split > 1) hipLaunchKernelGGL(sgemm_tn_reduce, dim3((a.flat + 255) / 256), dim3(256), 0, st, a);
     }
+    else if (split_form && mode == MDETR_SGEMM_NN && tsz_m == 32) MDETR_SGEMM_SPLIT_LAUNCH(MDETR_SGEMM_NN, 32, dim3(tiles))
+    else if (split_form && mode == MDETR_SGEMM_NN) MDETR_SGEMM_SPLIT_LAUNCH(MDETR_SGEMM_NN, 64, dim3(tiles))
+    else if (split_form && tsz_m == 32) MDETR_SGEMM_SPLIT_LAUNCH(MDETR_SGEMM_NT, 32, dim3(tiles))
+    else if (split_form) MDETR_SGEMM_SPLIT_LAUNCH(MDETR_SGEMM_NT, 64, dim3(tiles))
+#undef MDETR_SGEMM_SPLIT_LAUNCH
     else if (mode == MDETR_SGEMM_NN) hipLaunchKernelGGL(sgemm_kernel<true>, dim3(tiles), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(sgemm_kernel<false>, dim3(tiles), dim3(256), 0, st, a);
     return hipGetLastError();

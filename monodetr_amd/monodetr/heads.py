@@ -22,6 +22,13 @@ from .. import sgemm_ext
 ENABLED = os.environ.get("MDETR_HEADS") == "1"
 
 
+def _split_form(x):
+    """A bf16 input (the bf16 body) carries 8 significant bits: its level takes the three-way bf16 split form of the grouped kernels
+    (fp32-exact products to 2^-25, the bf16 matrix instruction) in all seven launches -- each measured faster than the exact form at
+    the training shape (profiles/r12a_headsbench.json); an fp32 input keeps the exact f32-input instruction."""
+    return x.dtype == torch.bfloat16
+
+
 def _heads_ok(x, bbox, dim, dep, ang, cls):
     from .depthaware_transformer import MLP
     if not ENABLED:
@@ -58,10 +65,10 @@ class _HeadsLevel(torch.autograd.Function):
         P, G = sgemm_ext.Problem, sgemm_ext.grouped
         sl = [slice(i * hid, (i + 1) * hid) for i in range(4)]                              # box | size | depth | angle
         G(sgemm_ext.NT, [P([(x2, w)], h1[:, s], bias=b, relu_cols=True) for w, b, s in zip((w1b, w1d, w1p, w1a), (b1b, b1d, b1p, b1a), sl)]
-          + [P([(x2, wc)], logits, bias=bc)])
+          + [P([(x2, wc)], logits, bias=bc)], split=_split_form(x))
         G(sgemm_ext.NT, [P([(h1[:, sl[0]], w2b)], h2, bias=b2b, relu_cols=True), P([(h1[:, sl[1]], wd)], size, bias=bd),
-                         P([(h1[:, sl[2]], wp)], depth, bias=bp), P([(h1[:, sl[3]], wa)], angle, bias=ba)])
-        G(sgemm_ext.NT, [P([(h2, w3b)], delta, bias=b3b)])
+                         P([(h1[:, sl[2]], wp)], depth, bias=bp), P([(h1[:, sl[3]], wa)], angle, bias=ba)], split=_split_form(x))
+        G(sgemm_ext.NT, [P([(h2, w3b)], delta, bias=b3b)], split=_split_form(x))
         ctx.save_for_backward(x, h1, h2, w1b, w2b, w3b, w1d, wd, w1p, wp, w1a, wa, wc)
         shape = lambda t: t.view(B, Q, -1)                                                  # noqa: E731
         return shape(delta), shape(size), shape(depth), shape(angle), shape(logits), x.view_as(x)
@@ -84,15 +91,17 @@ class _HeadsLevel(torch.autograd.Function):
         sl = [slice(i * hid, (i + 1) * hid) for i in range(4)]
         new = lambda *s: torch.empty(s, dtype=torch.float32, device=x.device)              # noqa: E731
         dh2, dh1 = new(T, hid), new(T, 4 * hid)
-        G(sgemm_ext.NN, [P([(g_delta, w3b)], dh2, mask=h2)])
-        G(sgemm_ext.NN, [P([(g, w)], dh1[:, s], mask=h1[:, s]) for g, w, s in zip((dh2, g_size, g_depth, g_angle), (w2b, wd, wp, wa), sl)])
+        G(sgemm_ext.NN, [P([(g_delta, w3b)], dh2, mask=h2)], split=_split_form(x))
+        G(sgemm_ext.NN, [P([(g, w)], dh1[:, s], mask=h1[:, s]) for g, w, s in zip((dh2, g_size, g_depth, g_angle), (w2b, wd, wp, wa), sl)],
+          split=_split_form(x))
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             skip = g_skip.reshape(T, C) if g_skip is not None else None
             if skip is not None and not (skip.stride(1) == 1 and skip.dtype in (torch.float32, torch.bfloat16)):
                 skip = skip.contiguous()
-            G(sgemm_ext.NN, [P([(dh1[:, s], w) for s, w in zip(sl, (w1b, w1d, w1p, w1a))] + [(g_logits, wc)], dx.view(T, C), res=skip)])
+            G(sgemm_ext.NN, [P([(dh1[:, s], w) for s, w in zip(sl, (w1b, w1d, w1p, w1a))] + [(g_logits, wc)], dx.view(T, C), res=skip)],
+              split=_split_form(x))
         # weight and bias gradients: one group of ten products over the token axis
         outs = {}
         jobs = []
@@ -103,7 +112,7 @@ class _HeadsLevel(torch.autograd.Function):
             dw, db = torch.empty_like(w), new(w.shape[0])
             outs[key] = (dw, db)
             jobs.append(P([(dy, act)], dw, colsum=db))
-        G(sgemm_ext.TN, jobs)
+        G(sgemm_ext.TN, jobs, split=_split_form(x))
         o = outs
         return (dx, o["1b"][0], o["1b"][1], o["2b"][0], o["2b"][1], o["3b"][0], o["3b"][1], o["1d"][0], o["1d"][1], o["d"][0], o["d"][1],
                 o["1p"][0], o["1p"][1], o["p"][0], o["p"][1], o["1a"][0], o["1a"][1], o["a"][0], o["a"][1], o["c"][0], o["c"][1])

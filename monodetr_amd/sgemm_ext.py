@@ -9,6 +9,7 @@ from . import _capi
 
 _backend = None               # tests substitute the CPU emulation of the same kernel source (tests/native_emul.py)
 NT, NN, TN = 0, 1, 2
+SPLIT = 16                    # MDETR_SGEMM_SPLIT, OR-ed into the mode: fp32 operands through the three-way bf16 split (bf16 matrix instruction)
 MAX_PROBLEMS, MAX_TERMS = 10, 5
 
 
@@ -63,8 +64,10 @@ class Problem:
         self.relu_cols = out.shape[1] if relu_cols is True else int(relu_cols)
 
 
-def grouped(mode, problems):
-    """Launch the group; every result tensor is written in place."""
+def grouped(mode, problems, split=False):
+    """Launch the group; every result tensor is written in place.  split: the three-way bf16 split form of csrc/sgemm.hip (fp32
+    operands as hi + mid + lo bf16 parts, six terms on the bf16 matrix instruction; products stay fp32-exact up to 2^-25 |a||b|;
+    an infinite operand gives NaN) instead of the exact f32-input instruction."""
     if not 0 < len(problems) <= MAX_PROBLEMS:
         raise ValueError("sgemm: 1 .. %d problems per group" % MAX_PROBLEMS)
     arr = (_Problem * len(problems))()
@@ -106,7 +109,8 @@ def grouped(mode, problems):
             assert pr.colsum.dtype == torch.float32 and pr.colsum.shape == (M,) and pr.colsum.is_contiguous()
             q.colsum = pr.colsum.data_ptr()
     parr = ctypes.cast(arr, ctypes.c_void_p)
-    need = _lib().mdetr_sgemm_workspace_bytes(mode, parr, len(problems)) if mode == TN else 0
+    base, mode = mode, (mode | SPLIT if split else mode)
+    need = _lib().mdetr_sgemm_workspace_bytes(mode, parr, len(problems)) if base == TN else 0
     ws = torch.empty(need, dtype=torch.uint8, device=dev) if need > 0 else None          # (scratch of this launch; the caching allocator recycles it)
     rc = -1 if need < 0 else _lib().mdetr_sgemm_grouped(mode, parr, len(problems), ws.data_ptr() if ws is not None else None, max(need, 0),
                                                         dev.index if dev.type == "cuda" else -1,
