@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MDETR_ABI_VERSION 18
+#define MDETR_ABI_VERSION 19
 
 /* element types of the floating-point tensors */
 #define MDETR_F32 0
@@ -806,6 +806,34 @@ int mdetr_fold_weights(int n, const void *const *w, const void *const *scale, vo
                        const int *O, const int *C, const int *taps, int device, void *stream);
 int mdetr_unfold_grads(int n, const void *const *dfolded, const void *const *scale, void *const *dw,
                        const int *O, const int *C, const int *taps, int device, void *stream);
+
+/*
+ * Packed and summed parameters in one launch (ABI 19; csrc/wpack.hip).  The transformer runs the projections of one input as one
+ * GEMM: an MSDeformAttn's sampling-offset and attention-weight projections (reference ops/modules/ms_deform_attn.py:138-141)
+ * concatenated, a decoder layer's content and position projections (depthaware_transformer.py:467-474) summed in weight space and
+ * concatenated.  Every row block of every packed tensor is one job:
+ *     dst[e] = src0[e]                                   (src1 == NULL)
+ *     dst[e] = (T)((float)src0[e] + (float)src1[e])      (one rounding: the bits of the framework's add), e < elements
+ * dtype MDETR_F32 / MDETR_BF16 per job (both may share a launch); pointers aligned to their element, nothing more: the
+ * destination is written in 16-byte pieces between its own 16-byte boundaries with a scalar head and tail.  `jobs` is a HOST
+ * array (the descriptors travel as kernel arguments, 48 per launch; a longer list takes several launches); elements == 0 is allowed.
+ */
+typedef struct {
+    void *dst;
+    const void *src0, *src1;
+    int64_t elements;
+    int32_t dtype, reserved;
+} mdetr_pack_job;
+int mdetr_pack_params(const mdetr_pack_job *jobs, int njobs, int device, void *stream);
+/*
+ * The encoder's level positions for one image (ABI 19): out[s][c] = sine[s][c] + level_embed[level of s][c] --
+ * cat_l(flatten(pos_l) + level_embed[l]).to(dtype) of the reference (depthaware_transformer.py:215-218) with the framework's
+ * arithmetic: the sum in fp32, rounded to bf16 where both operands are bf16, then converted to out_dtype.  sine [S][C] in
+ * sine_dtype, level_embed [levels][C] in embed_dtype, out [S][C]; counts[l] (HOST array) tokens belong to level l, S = their sum;
+ * levels <= 8, C a multiple of 8, 16-byte aligned tensors; dtypes MDETR_F32 / MDETR_BF16.
+ */
+int mdetr_level_pos(const void *sine, int sine_dtype, const void *level_embed, int embed_dtype, void *out, int out_dtype, const int64_t *counts,
+                    int levels, int C, int device, void *stream);
 
 /*
  * Gather of many dense device tensors into one flat device buffer (the optimizer's flat gradient buffer; the reference's AdamW

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MDETR_LIB_PATH") or os.path.join(_HERE, "libmonodetr_
 
 MDETR_F32, MDETR_F64, MDETR_BF16 = 0, 1, 2
 MDETR_E_UNSUPPORTED = -4
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _c_int, _c_vp = ctypes.c_int, ctypes.c_void_p
 
@@ -102,6 +102,8 @@ SIGNATURES = {
     "mdetr_gather_flat": (_c_int, [_c_vp, _c_int] + [_c_vp] * 6 + [_c_int, _c_int, _c_vp]),
     "mdetr_fold_weights": (_c_int, [_c_int] + [_c_vp] * 7 + [_c_int, _c_vp]),
     "mdetr_unfold_grads": (_c_int, [_c_int] + [_c_vp] * 6 + [_c_int, _c_vp]),
+    "mdetr_pack_params": (_c_int, [_c_vp, _c_int, _c_int, _c_vp]),
+    "mdetr_level_pos": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_vp]),
     "mdetr_maxpool3x3s2_bf16": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     "mdetr_decimate2": (_c_int, [_c_int, _c_vp, _c_vp, _c_int, _c_int, _c_int, ctypes.c_int64, _c_int, _c_vp]),
     "mdetr_msda_prologue_forward_packed": (_c_int, [_c_int, _c_int] + [_c_vp] * 5 + [_c_int] * 6 + [ctypes.c_int64] * 3 + [_c_int, _c_vp]),

@@ -18,15 +18,19 @@ LIB = os.path.join(HERE, "libmonodetr_amd.so")
 ARCH = "gfx950"
 
 
+# .hip files that another translation unit includes (wpack.hip: part of capi.hip, ABI 19): dependencies, not sources
+INCLUDED = [os.path.join(CSRC, "wpack.hip")]
+
+
 def sources():
-    return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+    return sorted(set(glob.glob(os.path.join(CSRC, "*.hip"))) - set(INCLUDED))
 
 
 def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h")) + [os.path.abspath(__file__)]
+    deps = sources() + INCLUDED + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h")) + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -71,7 +75,7 @@ def build(force=False, save_temps=False, verbose=False):
     same_flags = os.path.exists(stamp_file) and open(stamp_file).read().strip() == stamp
     if not force and same_flags and not _stale():
         return LIB
-    hdr_t = max(os.path.getmtime(d) for d in glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h")) + [os.path.abspath(__file__)])
+    hdr_t = max(os.path.getmtime(d) for d in INCLUDED + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(INCLUDE, "*.h")) + [os.path.abspath(__file__)])
     extra = ["-Rpass-analysis=kernel-resource-usage"] if save_temps else []
     jobs, objs = [], []
     for src in sources():

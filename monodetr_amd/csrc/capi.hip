@@ -37,6 +37,7 @@
 #include "msda.h"
 #include "msda_prologue.h"
 #include "msda_prologue_math.h"
+#include "wpack.hip"      // the parameter-packing kernels and their launchers are part of THIS translation unit (see the file's head)
 
 namespace {
 
@@ -1199,6 +1200,43 @@ int mdetr_unfold_grads(int n, const void *const *dfolded, const void *const *sca
     if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "mdetr_unfold_grads: set device %d: %s", device, hipGetErrorString(dev.err));
     const hipError_t e = mdetr::unfold_grads_launch(n, dfolded, scale, dw, O, C, taps, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(MDETR_E_HIP, "mdetr_unfold_grads: launch failed: %s", hipGetErrorString(e));
+    return MDETR_OK;
+}
+
+int mdetr_pack_params(const mdetr_pack_job *jobs, int njobs, int device, void *stream)
+{
+    if (njobs == 0) return MDETR_OK;
+    const char *why = mdetr::pack_params_check(jobs, njobs);
+    if (why) return fail(MDETR_E_ARG, "mdetr_pack_params: %s (%d jobs)", why, njobs);
+    DeviceScope dev(device);
+    if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "mdetr_pack_params: set device %d: %s", device, hipGetErrorString(dev.err));
+    const hipError_t e = mdetr::pack_params_launch(jobs, njobs, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MDETR_E_HIP, "mdetr_pack_params: launch failed: %s", hipGetErrorString(e));
+    return MDETR_OK;
+}
+
+int mdetr_level_pos(const void *sine, int sine_dtype, const void *level_embed, int embed_dtype, void *out, int out_dtype, const int64_t *counts,
+                    int levels, int C, int device, void *stream)
+{
+    if ((sine_dtype != MDETR_F32 && sine_dtype != MDETR_BF16) || (embed_dtype != MDETR_F32 && embed_dtype != MDETR_BF16) ||
+        (out_dtype != MDETR_F32 && out_dtype != MDETR_BF16))
+        return fail(MDETR_E_ARG, "mdetr_level_pos: dtypes must be MDETR_F32 or MDETR_BF16");
+    if (!counts || levels <= 0 || levels > mdetr::kPosLevels || C <= 0 || C % 8 != 0)
+        return fail(MDETR_E_ARG, "mdetr_level_pos: levels=%d (1 .. %d) C=%d (a positive multiple of 8)", levels, mdetr::kPosLevels, C);
+    int64_t S = 0;
+    for (int l = 0; l < levels; ++l) {
+        if (counts[l] < 0) return fail(MDETR_E_ARG, "mdetr_level_pos: level %d has %lld tokens", l, static_cast<long long>(counts[l]));
+        S += counts[l];
+    }
+    if (S == 0) return MDETR_OK;
+    if (S * (C / 8) >= (1ll << 38)) return fail(MDETR_E_ARG, "mdetr_level_pos: S * C too large");
+    if (!sine || !level_embed || !out) return fail(MDETR_E_ARG, "mdetr_level_pos: null pointer");
+    if (!aligned16(sine) || !aligned16(level_embed) || !aligned16(out)) return fail(MDETR_E_ALIGN, "mdetr_level_pos: tensors must be 16-byte aligned");
+    DeviceScope dev(device);
+    if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "mdetr_level_pos: set device %d: %s", device, hipGetErrorString(dev.err));
+    const hipError_t e = mdetr::level_pos_launch(sine, sine_dtype == MDETR_BF16, level_embed, embed_dtype == MDETR_BF16, out, out_dtype == MDETR_BF16, counts, levels, C,
+                                                 static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MDETR_E_HIP, "mdetr_level_pos: launch failed: %s", hipGetErrorString(e));
     return MDETR_OK;
 }
 

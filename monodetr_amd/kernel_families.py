@@ -14,7 +14,7 @@ AUTOTUNE_SWITCHES = ("MDETR_FUSED_LOSSES", "MDETR_FUSED_ADAMW", "MDETR_MSDA_PROL
                      "MDETR_FUSED_EPILOGUE", "MDETR_GEMM_RELU", "MDETR_CONV3X3", "MDETR_GROUP_NORM", "MDETR_SMALL_WGRAD",
                      "MDETR_CONV_STRIDED", "MDETR_CONV_WGRAD", "MDETR_CONV_STEM", "MDETR_TGEMM", "MDETR_WFOLD", "MDETR_RELU_PREMASK",
                      "MDETR_HEADS", "MDETR_CHUNK_SUMS", "MDETR_HEAD_TAIL", "MDETR_TGEMM_F32", "MDETR_TWGRAD_F32",
-                     "MDETR_CONV3X3_F32", "MDETR_CONV_WGRAD_F32", "MDETR_CONV_STRIDED_F32")
+                     "MDETR_CONV3X3_F32", "MDETR_CONV_WGRAD_F32", "MDETR_CONV_STRIDED_F32", "MDETR_PARAM_PACK")
 ALL_SWITCHES = AUTOTUNE_SWITCHES
 # The measured configuration.  family -> the GPU tests that hold it to the default path / the framework operators
 # (all in tests/test_fused_gpu.py unless a file is named); a family without green tests is not listed.
@@ -42,6 +42,7 @@ SWITCH_TESTS = {
     "MDETR_HEADS": "test_sgemm_gpu.py::test_sgemm_*, test_sgemm_gpu.py::test_heads_level_*, test_training_step_with_the_grouped_heads_*, test_exact_products_gpu.py::test_exact_sgemm_grouped_*",
     "MDETR_HEAD_TAIL": "test_sgemm_gpu.py::test_head_tail_*, test_sgemm_gpu.py::test_training_step_with_the_head_tail_*, test_head_tail_cases_gpu.py::test_head_tail_*",
     "MDETR_CHUNK_SUMS": "test_colsum_gpu.py::test_chunk_sums_*, test_colsum_gpu.py::test_deferred_chunk_sums_*, test_chunk_sums_tall_gpu.py::test_chunk_sums_*",
+    "MDETR_PARAM_PACK": "test_wpack_gpu.py::test_*",
     "MDETR_CONV3X3": "test_conv3x3_kernel_matches_the_library_convolution, test_training_step_with_the_conv3x3_kernel_*, test_conv3x3_module_with_a_trainable_bias_*, test_exact_products_gpu.py::test_exact_conv3x3_*",
 }
 COMMITTED_SWITCHES = {
@@ -71,13 +72,15 @@ COMMITTED_SWITCHES = {
     # MDETR_CONV_STRIDED_F32: the fp32 3x3 / stride-2 convolutions (forward and input gradient) through the fp32 form of
     # csrc/conv_taps.hip (mdetr_conv_taps_f32, mdetr_conv_dgrad_s2_f32); the weight gradient stays on the library.  Opt-in: on NO
     # committed list; DESIGN.md 3.5 records what was measured.
+    # MDETR_PARAM_PACK: the transformer's packed / summed projection parameters of a forward pass from one launch and the encoder's
+    # level positions as one [S, C] tensor from one more (csrc/wpack.hip), bit-identical; DESIGN.md 3.7 records the launches and the step.
     "bf16": ("MDETR_FUSED_LOSSES", "MDETR_FUSED_ADAMW", "MDETR_FUSED_LN", "MDETR_MSDA_PROLOGUE", "MDETR_MSDA_BF16",
              "MDETR_FUSED_EPILOGUE", "MDETR_GEMM_RELU", "MDETR_CONV3X3", "MDETR_GROUP_NORM", "MDETR_SMALL_WGRAD",
              "MDETR_CONV_WGRAD", "MDETR_CONV_STRIDED", "MDETR_CONV_STEM", "MDETR_TGEMM", "MDETR_WFOLD", "MDETR_RELU_PREMASK", "MDETR_HEADS",
-             "MDETR_CHUNK_SUMS", "MDETR_HEAD_TAIL"),
+             "MDETR_CHUNK_SUMS", "MDETR_HEAD_TAIL", "MDETR_PARAM_PACK"),
     "fp32": ("MDETR_FUSED_LOSSES", "MDETR_FUSED_ADAMW", "MDETR_FUSED_LN", "MDETR_MSDA_PROLOGUE",
              "MDETR_FUSED_EPILOGUE", "MDETR_GEMM_RELU", "MDETR_GROUP_NORM", "MDETR_SMALL_WGRAD", "MDETR_HEADS",
-             "MDETR_HEAD_TAIL"),
+             "MDETR_HEAD_TAIL", "MDETR_PARAM_PACK"),
 }
 COMMITTED_SWITCHES["bf16-autocast"] = COMMITTED_SWITCHES["fp32"]
 
@@ -100,7 +103,7 @@ def apply_switches(names):
     from monodetr_amd import chunk_sums, head_tail_ext
     chunk_sums.ENABLED = "MDETR_CHUNK_SUMS" in names
     head_tail_ext.ENABLED = "MDETR_HEAD_TAIL" in names
-    from monodetr_amd import add_ln_ext, bias_act_ext, conv3x3_ext, conv_stem_ext, conv_taps_ext, conv_wgrad_ext, group_norm_ext, small_wgrad_ext, wfold_ext
+    from monodetr_amd import add_ln_ext, bias_act_ext, conv3x3_ext, conv_stem_ext, conv_taps_ext, conv_wgrad_ext, group_norm_ext, small_wgrad_ext, wfold_ext, wpack_ext
     from monodetr_amd.monodetr import heads, linear
     from monodetr_amd.monodetr.ops.functions import ms_deform_attn_func
     from monodetr_amd.monodetr.ops.modules import ms_deform_attn
@@ -110,6 +113,7 @@ def apply_switches(names):
     linear._TGEMM_F32 = "MDETR_TGEMM_F32" in names
     heads.ENABLED = "MDETR_HEADS" in names
     wfold_ext.ENABLED = "MDETR_WFOLD" in names
+    wpack_ext.ENABLED = "MDETR_PARAM_PACK" in names
     linear._PREMASK = "MDETR_RELU_PREMASK" in names
     linear._GEMM_RELU = "MDETR_GEMM_RELU" in names
     bias_act_ext.ENABLED = "MDETR_FUSED_EPILOGUE" in names

@@ -471,6 +471,8 @@ class Joiner(nn.Sequential):
         hit = casts.get(key)
         if hit is None or hit[0] is not p or hit[1] != p._version:
             hit = casts[key] = (p, p._version, p.to(dt), hit)          # (a superseded entry stays referenced: see above)
+            if getattr(p, "_mdetr_sine_const", False):
+                hit[2]._mdetr_sine_const = True
         return hit[2]
 
     def forward(self, images):

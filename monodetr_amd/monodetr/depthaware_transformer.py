@@ -115,6 +115,26 @@ class _SummedPair(torch.autograd.Function):
         return gw[:n], gw[:n], gw[n:], gw[n:], gb[:n], gb[:n], gb[n:], gb[n:]
 
 
+_SINE_FLAT = {}
+
+
+def _shared_sine(pos_embeds):
+    """The constant position encodings of ONE image, flattened and concatenated along the token axis -- [S, C], made once per set of
+    encodings -- or None.  Only where the map is provably the same for every image and every call: each level is the cached tensor
+    the sine encoding returns for an unpadded batch of that shape (position_encoding.py marks it, backbone.Joiner its cast)."""
+    from .. import wpack_ext
+    if not (pos_embeds and wpack_ext.available(pos_embeds[0])
+            and all(getattr(p, "_mdetr_sine_const", False) and p.dtype == pos_embeds[0].dtype and p.dim() == 4 for p in pos_embeds)):
+        return None
+    key = tuple(id(p) for p in pos_embeds)              # (the entry keeps the tensors: their ids stay theirs)
+    hit = _SINE_FLAT.get(key)
+    if hit is None or any(p._version != v for p, v in hit[0]):
+        with torch.no_grad():
+            flat = torch.cat([p[0].flatten(1).t() for p in pos_embeds], 0).contiguous()
+        hit = _SINE_FLAT[key] = ([(p, p._version) for p in pos_embeds], flat)
+    return hit[1]
+
+
 class _LevelPos(torch.autograd.Function):
     """cat_l(flatten(pos_l) + level_embed[l]) along the token axis, as ``dtype`` (reference depthaware_transformer.py:215-218).
     The sine embeddings are constants; the only gradient is level_embed's, a sum over the batch and the level's tokens.  As
@@ -127,6 +147,14 @@ class _LevelPos(torch.autograd.Function):
         ctx.counts = [p.shape[-2] * p.shape[-1] for p in pos]
         ctx.embed_dtype = level_embed.dtype
         ctx.pos_meta = [(p.shape, p.dtype) for p in pos]
+        # where every image has the same constant encodings (`_shared_sine`): ONE [S, C] tensor from one launch (csrc/wpack.hip, bit
+        # for bit the expression below) with a stride-0 batch axis
+        shared = _shared_sine(pos)
+        if shared is not None:
+            from .. import wpack_ext
+            if wpack_ext.level_pos_supported(shared, level_embed, ctx.counts, dtype):
+                one = wpack_ext.level_positions(shared, level_embed, ctx.counts, dtype)
+                return one.unsqueeze(0).expand(pos[0].shape[0], -1, -1)
         return torch.cat([p.flatten(2).transpose(1, 2) + level_embed[l].view(1, 1, -1) for l, p in enumerate(pos)], 1).to(dtype)
 
     @staticmethod
@@ -284,11 +312,21 @@ class DepthAwareDecoderLayer(nn.Module):
 
     def _self_attention_inputs(self, x):
         """q = (Wqc + Wqp) x + b, k = (Wkc + Wkp) x + b : the four projections of the reference
-        (:467-474) act on the same input, so they are summed in weight space -- ONE GEMM, not 4."""
-        w, b = _SummedPair.apply(self.sa_qcontent_proj.weight, self.sa_qpos_proj.weight, self.sa_kcontent_proj.weight, self.sa_kpos_proj.weight,
-                                 self.sa_qcontent_proj.bias, self.sa_qpos_proj.bias, self.sa_kcontent_proj.bias, self.sa_kpos_proj.bias)
+        (:467-474) act on the same input, so they are summed in weight space -- ONE GEMM, not 4.  Inside `DepthAwareTransformer`
+        the summed pair arrives packed for this forward pass (`_pack_site`, one launch for every layer)."""
+        handed = self.__dict__.pop("_packed_now", None)
+        if handed is not None:
+            w, b = handed
+        else:
+            w, b = _SummedPair.apply(self.sa_qcontent_proj.weight, self.sa_qpos_proj.weight, self.sa_kcontent_proj.weight, self.sa_kpos_proj.weight,
+                                     self.sa_qcontent_proj.bias, self.sa_qpos_proj.bias, self.sa_kcontent_proj.bias, self.sa_kpos_proj.bias)
         q, k = token_linear(x, w, b).split(x.shape[-1], -1)
         return q, k
+
+    def _pack_site(self):
+        """(weight row blocks, bias row blocks) of `_self_attention_inputs` for `wpack_ext.pack_sites`: two summed pairs each."""
+        return (((self.sa_qcontent_proj.weight, self.sa_qpos_proj.weight), (self.sa_kcontent_proj.weight, self.sa_kpos_proj.weight)),
+                ((self.sa_qcontent_proj.bias, self.sa_qpos_proj.bias), (self.sa_kcontent_proj.bias, self.sa_kpos_proj.bias)))
 
     def forward(self, tgt, query_pos, reference_points, src, src_spatial_shapes, level_start_index,
                 src_padding_mask, depth_pos_embed, mask_depth, bs, query_sine_embed=None, is_first=None,
@@ -453,6 +491,29 @@ class DepthAwareTransformer(nn.Module):
             hit = self._shape_cache[key] = (ss, torch.cat((ss.new_zeros((1,)), ss.prod(1).cumsum(0)[:-1])))
         return hit
 
+    def _pack_parameters(self, like):
+        """Every packed projection of this forward pass from ONE launch (csrc/wpack.hip): {module: (weight, bias)} for the encoder's
+        deformable attentions and for the decoder's (layers and their cross attentions).  Empty where the family is off, under
+        autocast or off the device: the modules then pack for themselves."""
+        from .. import wpack_ext
+        if not wpack_ext.available(like):
+            return {}, {}
+        enc = [layer.self_attn for layer in self.encoder.layers]
+        dec = [m for layer in self.decoder.layers for m in (layer, layer.cross_attn)]
+        sites = [(m,) + m._pack_site() for m in enc + dec if m._pack_site() is not None]
+        packed = wpack_ext.pack_sites(sites)
+        return {m: packed[m] for m in enc if m in packed}, {m: packed[m] for m in dec if m in packed}
+
+    @staticmethod
+    def _hand_out(packed):
+        for m, pair in packed.items():
+            m.__dict__["_packed_now"] = pair
+
+    @staticmethod
+    def _take_back(packed):
+        for m in packed:
+            m.__dict__.pop("_packed_now", None)
+
     def encode(self, srcs, masks, pos_embeds):
         """Flatten + concatenate the pyramid and run the visual encoder (depthaware_transformer.py:208-229 of the
         reference): returns (memory [B, S, C], spatial_shapes, level_start_index, valid_ratios, mask_flatten, mask_depth).
@@ -470,8 +531,15 @@ class DepthAwareTransformer(nn.Module):
             valid_ratios = torch.stack([self.get_valid_ratio(m) for m in masks], 1)
             mask_depth = masks[1].flatten(1)
 
-        memory = self.encoder(src_flatten, spatial_shapes, level_start_index, valid_ratios, lvl_pos, mask_flatten,
-                              shape_list=shapes)
+        # the packed projections of the whole forward pass, the decoder's included: `forward` hands those out after this call, a
+        # caller of `encode` alone (`bench.py --config 2`) never does, and their sources then get no gradient
+        for_encoder, self.__dict__["_decoder_packs"] = self._pack_parameters(src_flatten)
+        self._hand_out(for_encoder)
+        try:
+            memory = self.encoder(src_flatten, spatial_shapes, level_start_index, valid_ratios, lvl_pos, mask_flatten,
+                                  shape_list=shapes)
+        finally:
+            self._take_back(for_encoder)
         return memory, spatial_shapes, level_start_index, valid_ratios, mask_flatten, mask_depth
 
     def forward(self, srcs, masks, pos_embeds, query_embed=None, depth_pos_embed=None, depth_pos_embed_ip=None,
@@ -479,6 +547,7 @@ class DepthAwareTransformer(nn.Module):
         assert query_embed is not None
         B, C = srcs[0].shape[:2]
         memory, spatial_shapes, level_start_index, valid_ratios, mask_flatten, mask_depth = self.encode(srcs, masks, pos_embeds)
+        for_decoder = self.__dict__.pop("_decoder_packs", {})
 
         # queries: first half of the embedding is the positional part, second half the content
         query_pos, tgt = torch.split(query_embed, C, dim=1)
@@ -490,10 +559,14 @@ class DepthAwareTransformer(nn.Module):
 
         depth_tokens = depth_pos_embed.flatten(2).permute(2, 0, 1)
         depth_tokens_ip = depth_pos_embed_ip.flatten(2).permute(2, 0, 1)
-        hs, inter_references, inter_references_dim = self.decoder(
-            tgt, reference_points, memory, spatial_shapes, level_start_index, valid_ratios, query_pos,
-            mask_flatten, depth_tokens, mask_depth, bs=B, depth_pos_embed_ip=depth_tokens_ip,
-            pos_embeds=pos_embeds, attn_mask=attn_mask)
+        self._hand_out(for_decoder)
+        try:
+            hs, inter_references, inter_references_dim = self.decoder(
+                tgt, reference_points, memory, spatial_shapes, level_start_index, valid_ratios, query_pos,
+                mask_flatten, depth_tokens, mask_depth, bs=B, depth_pos_embed_ip=depth_tokens_ip,
+                pos_embeds=pos_embeds, attn_mask=attn_mask)
+        finally:
+            self._take_back(for_decoder)
         return hs, init_reference_out, inter_references, inter_references_dim, None, None
 
 

@@ -145,7 +145,8 @@ class MonoDETR(nn.Module):
         for l in range(len(srcs), self.num_feature_levels):        # extra stride-2 levels (:166-178)
             src = self.input_proj[l](features[-1].tensors if l == len(features) else srcs[-1])
             mask = mark_no_padding(torch.zeros((src.shape[0],) + tuple(src.shape[-2:]), dtype=torch.bool, device=src.device))
-            pos.append(self.backbone[1](NestedTensor(src, mask)).to(src.dtype))
+            level = NestedTensor(src, mask)
+            pos.append(self.backbone._as(level, self.backbone[1](level), src.dtype))     # (a constant encoding's cast is kept, as the backbone levels')
             srcs.append(src)
             masks.append(mask)
         return srcs, masks, pos

@@ -133,9 +133,21 @@ class MSDeformAttn(nn.Module):
 
     def _packed_projection(self):
         """The two projections of the query as ONE GEMM (384 = 256 offset + 128 logit columns): one read of the query forward,
-        one input-gradient GEMM and one weight-gradient GEMM backward, and no sum of two query gradients."""
+        one input-gradient GEMM and one weight-gradient GEMM backward, and no sum of two query gradients.  Inside
+        `DepthAwareTransformer` the pair arrives packed for this forward pass (`_pack_site`, one launch for every module)."""
+        handed = self.__dict__.pop("_packed_now", None)
+        if handed is not None:
+            return handed
         return (torch.cat((self.sampling_offsets.weight, self.attention_weights.weight), 0),
                 torch.cat((self.sampling_offsets.bias, self.attention_weights.bias), 0))
+
+    def _pack_site(self):
+        """(weight row blocks, bias row blocks) of `_packed_projection` for `wpack_ext.pack_sites`, or None where `forward` /
+        `forward_self` would not ask for the packed pair."""
+        if not (_FUSED_PROLOGUE and _PACKED_PROJECTION):
+            return None
+        return (((self.sampling_offsets.weight,), (self.attention_weights.weight,)),
+                ((self.sampling_offsets.bias,), (self.attention_weights.bias,)))
 
     def _attend(self, value, packed, offsets, logits, reference_points, input_spatial_shapes, input_level_start_index, out_dtype,
                 value_token=None):

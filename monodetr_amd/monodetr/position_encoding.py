@@ -33,6 +33,7 @@ class PositionEmbeddingSine(nn.Module):
         pos = self._cache.get(key)
         if pos is None:
             pos = self._cache[key] = self._encode(mask)
+            pos._mdetr_sine_const = True      # the same tensor on every call, the same map for every image (`_LevelPos`)
         return pos
 
     def _encode(self, mask):
