@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MDETR_ABI_VERSION 19
+#define MDETR_ABI_VERSION 20
 
 /* element types of the floating-point tensors */
 #define MDETR_F32 0
@@ -737,6 +737,18 @@ int mdetr_conv_wgrad(const void *x, const void *dy, float *partial, int64_t part
 int mdetr_conv_wgrad_f32_chunks(int B, int H, int W, int C, int OH, int OW, int N, int K, int SI);
 int mdetr_conv_wgrad_f32(const void *x, const void *dy, float *partial, int64_t partial_floats, int B, int H, int W, int C, int OH, int OW, int N,
                          int K, int SI, int device, void *stream);
+/* The fp32 form at stride 2 (ABI 20; csrc/conv_wgrad.hip, conv_wgrad_s2_f32_kernel) for the 3x3 / stride-2 / pad-1 convolutions of the
+ * fp32 configurations (layer2.0 / layer3.0 / layer4.0 conv2, the depth predictor's downsample):
+ *   dW[n, t, e, c] = sum_{b, r, q} dy[b, r, q, n] * x[b, 2 r + t - 1, 2 q + e - 1, c]
+ * The split, the six terms and their order, the partial layout and the chunk-sum contract are mdetr_conv_wgrad_f32's; the pixel tile
+ * is 8 rows x 8 columns and the workgroup's weight block 64 n x 64 c.  Deterministic, no atomics; an infinite operand yields NaN.
+ *   K == 3, SI == 2, OH == (H - 1) / 2 + 1, OW == (W - 1) / 2 + 1 only;  x  fp32 [B, H, W, C], C % 64 == 0;  dy  fp32 [B, OH, OW, N],
+ *   N % 32 == 0; both 16-byte aligned;  B H W C and B OH OW N below 2^29 elements (judged before any pointer is looked at), 9 N C below
+ *   2^28.  Anything else, an empty problem included: MDETR_E_ARG, and mdetr_conv_wgrad_s2_f32_chunks returns 0.  MDETR_TUNE key
+ *   conv_wgrad_wgs (workgroups to aim for; this form aims for 512 without it, two per CU) applies as to the other entries. */
+int mdetr_conv_wgrad_s2_f32_chunks(int B, int H, int W, int C, int OH, int OW, int N, int K, int SI);
+int mdetr_conv_wgrad_s2_f32(const void *x, const void *dy, float *partial, int64_t partial_floats, int B, int H, int W, int C, int OH, int OW, int N,
+                            int K, int SI, int device, void *stream);
 
 /*
  * Weight AND bias gradient of a token-wise linear layer y = x W^T + b over T token rows (autograd of the nn.Linear / 1x1

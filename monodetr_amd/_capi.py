@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MDETR_LIB_PATH") or os.path.join(_HERE, "libmonodetr_
 
 MDETR_F32, MDETR_F64, MDETR_BF16 = 0, 1, 2
 MDETR_E_UNSUPPORTED = -4
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _c_int, _c_vp = ctypes.c_int, ctypes.c_void_p
 
@@ -80,6 +80,8 @@ SIGNATURES = {
     "mdetr_conv_wgrad": (_c_int, [_c_vp] * 3 + [ctypes.c_int64] + [_c_int] * 9 + [_c_int, _c_vp]),
     "mdetr_conv_wgrad_f32_chunks": (_c_int, [_c_int] * 9),
     "mdetr_conv_wgrad_f32": (_c_int, [_c_vp] * 3 + [ctypes.c_int64] + [_c_int] * 9 + [_c_int, _c_vp]),
+    "mdetr_conv_wgrad_s2_f32_chunks": (_c_int, [_c_int] * 9),
+    "mdetr_conv_wgrad_s2_f32": (_c_int, [_c_vp] * 3 + [ctypes.c_int64] + [_c_int] * 9 + [_c_int, _c_vp]),
     "mdetr_token_wgrad_chunks": (_c_int, [ctypes.c_int64, _c_int, _c_int]),
     "mdetr_token_wgrad": (_c_int, [_c_vp, _c_vp, _c_vp, ctypes.c_int64, ctypes.c_int64, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     "mdetr_token_wgrad_f32_chunks": (_c_int, [ctypes.c_int64, _c_int, _c_int]),

@@ -5,7 +5,8 @@ run on that kernel -- the input gradient as the four pixel-parity classes of the
 with 1x1 / 1x2 / 2x1 / 2x2 taps --, the weight gradient on csrc/conv_wgrad.hip (conv_wgrad_ext).
 
 With MDETR_CONV_STRIDED_F32=1 fp32 tensors take the fp32 form of the same kernel for the 3x3 case (``mdetr_conv_taps_f32``,
-``mdetr_conv_dgrad_s2_f32``: three-way bf16 split, fp32-accurate) and return fp32; their weight gradient stays on the library."""
+``mdetr_conv_dgrad_s2_f32``: three-way bf16 split, fp32-accurate) and return fp32; their weight gradient is the library's unless
+MDETR_CONV_WGRAD_S2_F32=1 sends it to ``mdetr_conv_wgrad_s2_f32`` (conv_wgrad_ext.supported_f32_s2)."""
 import os
 
 import torch
@@ -222,7 +223,8 @@ class _ConvStrided(torch.autograd.Function):
                 dx = torch.ops.aten.convolution_backward(dy, x, weight, None, (2, 2), pad, (1, 1), False, (0, 0), 1, (True, False, False))[0]
         if ctx.needs_input_grad[1]:
             from . import conv_wgrad_ext
-            if conv_wgrad_ext.supported(x, dy, k, 2):
+            # (fp32: the stride-2 form of the weight-gradient kernel where its family is on -- whichever route forward and dX took)
+            if conv_wgrad_ext.supported(x, dy, k, 2) or (k == 3 and weight.dtype == torch.float32 and conv_wgrad_ext.supported_f32_s2(x, dy)):
                 dw = conv_wgrad_ext.weight_gradient(x, dy, k, 2, weight.dtype, like=weight)
             else:
                 dw = torch.ops.aten.convolution_backward(dy, x, weight, None, (2, 2), pad, (1, 1), False, (0, 0), 1, (False, True, False))[1]

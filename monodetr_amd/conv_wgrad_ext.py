@@ -1,7 +1,8 @@
 """``weight_gradient(x, dy, k, stride, dtype)``: dW of a 3x3 (stride 1 / 2, pad 1) or 1x1 (stride 2) convolution from the
 channels_last bf16 activation and output gradient (csrc/conv_wgrad.hip through ``mdetr_conv_wgrad``: split-K over pixel tiles
 on the matrix cores; the per-chunk partial gradients are added in a fixed order by csrc/colsum.hip, one rounding).  fp32 operands
-of a 3x3 / stride-1 convolution take the fp32 form of the kernel (``mdetr_conv_wgrad_f32``, MDETR_CONV_WGRAD_F32=1)."""
+of a 3x3 / stride-1 convolution take the fp32 form of the kernel (``mdetr_conv_wgrad_f32``, MDETR_CONV_WGRAD_F32=1), those of a
+3x3 / stride-2 convolution its stride-2 sibling (``mdetr_conv_wgrad_s2_f32``, MDETR_CONV_WGRAD_S2_F32=1)."""
 import os
 
 import torch
@@ -52,6 +53,36 @@ def supported_f32(x, dy, k, stride):
             and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0)
 
 
+# Which fp32 STRIDE-2 shape classes take the kernel (mdetr_conv_wgrad_s2_f32): tools/convbench --dtype fp32 --only wgrad, the stride-2 rows
+# (profiles/r14a_convbench_fp32_wgrad_s2.json; kernel + chunk sum against aten.convolution_backward at stride 2, B = 8, medians of 3 captures
+# [min, max], us):
+#   layer2.0.conv2  128 -> 128 from 96 x 320   142.4 [141.9, 144.1]  against  172.0 [168.3, 177.3]   ahead  (4 blocks of 64 n x 64 c, 42 chunks)
+#   layer3.0.conv2  256 -> 256 from 48 x 160   142.7 [141.2, 142.9]  against  166.3 [162.9, 175.1]   ahead  (16 blocks, 10 chunks; the depth
+#                                                                                                   predictor's downsample is this problem)
+#   layer4.0.conv2  512 -> 512 from 24 x 80    194.6 [194.0, 195.3]  against  169.8 [164.8, 174.2]   behind: 64 blocks x 3 tap rows leave 2 chunks,
+#                                                                                                   384 workgroups on 512 places
+# A class whose median is not ahead of the library's own [min, max] stays on the library: more than 16 (64 n x 64 c) weight blocks (layer3.0
+# has 16, layer4.0 64; nothing between them was measured, so nothing between them is admitted).  Nothing below 128 output channels was
+# measured either -- the model has no such site -- so nothing below is admitted.
+_F32_S2_MIN_N = 128
+_F32_S2_MAX_BLOCKS = 16
+
+
+def supported_f32_s2(x, dy):
+    """fp32 channels_last operands of a 3x3 / stride-2 / pad-1 convolution (x [B, C, H, W], dy [B, N, (H - 1) // 2 + 1, (W - 1) // 2 + 1]) within
+    the entry's limits (C % 64 == 0, N % 32 == 0, 16-byte aligned, both operands below 2^29 elements, 9 N C below 2^28) and the measured
+    shape rule above, with the family MDETR_CONV_WGRAD_S2_F32 on -- also under the emulated kernel (tests): the family alone decides, so
+    that the fp32 strided convolutions keep the library's weight gradient without it."""
+    return (ENABLED_CONV_S2_F32 and (x.is_cuda or _backend is not None) and x.dim() == 4 and dy.dim() == 4 and x.dtype == torch.float32
+            and dy.dtype == torch.float32 and x.shape[1] % 64 == 0 and dy.shape[1] % 32 == 0
+            and x.numel() > 0 and dy.numel() > 0 and x.shape[0] == dy.shape[0]
+            and tuple(dy.shape[2:]) == ((x.shape[2] - 1) // 2 + 1, (x.shape[3] - 1) // 2 + 1)
+            and x.numel() < (1 << 29) and dy.numel() < (1 << 29) and dy.shape[1] * 9 * x.shape[1] < (1 << 28)
+            and dy.shape[1] >= _F32_S2_MIN_N and ((dy.shape[1] + 63) // 64) * (x.shape[1] // 64) <= _F32_S2_MAX_BLOCKS
+            and x.is_contiguous(memory_format=torch.channels_last) and dy.is_contiguous(memory_format=torch.channels_last)
+            and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0)
+
+
 # Weight AND bias gradients of token-wise linear layers over tens of thousands of rows (the encoder's 81 600, the backbone's 1x1
 # convolutions) as the 1x1 case of this kernel, the bias gradient riding along (mdetr_token_wgrad), instead of the library's batched
 # split-K product + chunk sum + two-launch column sum: 53 -> 43 us at [81 600, 256] x [81 600, 256], 49 -> 28-36 us on the backbone's
@@ -66,6 +97,11 @@ ENABLED_F32 = os.environ.get("MDETR_TWGRAD_F32") == "1"
 # (MIOpen igemm_wrw / CK bwd_weight).  Consulted in conv3x3_ext._Conv3x3.backward only, so in the step it acts together with
 # MDETR_CONV3X3_F32.  A family of its own, opt-in, on no committed list.
 ENABLED_CONV_F32 = os.environ.get("MDETR_CONV_WGRAD_F32") == "1"
+# MDETR_CONV_WGRAD_S2_F32=1: the weight gradient of the FP32 3x3 / stride-2 convolutions through conv_wgrad_s2_f32_kernel
+# (mdetr_conv_wgrad_s2_f32: the same split and six terms on a tile of its own) instead of the library's.  Consulted in
+# conv_taps_ext._ConvStrided.backward only, so in the step it acts together with MDETR_CONV_STRIDED_F32.  A family of its own, opt-in,
+# on no committed list.
+ENABLED_CONV_S2_F32 = os.environ.get("MDETR_CONV_WGRAD_S2_F32") == "1"
 
 
 def _chunk_sum_route(chunk_sums, cuda, cols, dtype):
@@ -152,7 +188,7 @@ def _stolen(like, N, C, k):
 
 
 def weight_gradient(x, dy, k, stride, dtype=torch.bfloat16, like=None):
-    """x [B, C, H, W], dy [B, N, OH, OW] (channels_last, both bf16 or -- k = 3, stride 1 -- both fp32) -> dW [N, C, k, k] in ``dtype``
+    """x [B, C, H, W], dy [B, N, OH, OW] (channels_last, both bf16 or -- k = 3, stride 1 or 2 -- both fp32) -> dW [N, C, k, k] in ``dtype``
     (channels_last strides).
     like: the weight the gradient is for; a leaf whose strides are not the result's gets its sum at once, never deferred (chunk_sums.py)."""
     B, C, H, W = x.shape
@@ -160,8 +196,8 @@ def weight_gradient(x, dy, k, stride, dtype=torch.bfloat16, like=None):
     lib = _lib()
     if x.dtype != dy.dtype or x.dtype not in (torch.bfloat16, torch.float32):
         raise RuntimeError("conv_wgrad: operands of one dtype, bf16 or fp32 (got %s, %s)" % (x.dtype, dy.dtype))
-    # fp32 operands: the fp32 form of the kernel (three-way bf16 split), same partials and chunk sums
-    entry = "mdetr_conv_wgrad_f32" if x.dtype == torch.float32 else "mdetr_conv_wgrad"
+    # fp32 operands: the fp32 forms of the kernel (three-way bf16 split; 3x3 / stride 2 has an entry of its own), same partials and chunk sums
+    entry = "mdetr_conv_wgrad" if x.dtype != torch.float32 else "mdetr_conv_wgrad_s2_f32" if (k, stride) == (3, 2) else "mdetr_conv_wgrad_f32"
     chunks = getattr(lib, entry + "_chunks")(B, H, W, C, OH, OW, N, k, stride)
     if chunks <= 0:
         raise RuntimeError("conv_wgrad: unsupported problem")

@@ -1020,6 +1020,39 @@ int mdetr_conv_wgrad_f32(const void *x, const void *dy, float *partial, int64_t 
     return MDETR_OK;
 }
 
+// The fp32 form at stride 2 (conv_wgrad_s2_f32_kernel): 3x3 taps, stride 2, pad 1.  Sizes are judged before any pointer is looked at.
+int mdetr_conv_wgrad_s2_f32_chunks(int B, int H, int W, int C, int OH, int OW, int N, int K, int SI)
+{
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || OH <= 0 || OW <= 0 || N <= 0) return 0;
+    const mdetr::ConvWgradDims d = wgrad_dims(B, H, W, C, OH, OW, N, K, SI);
+    if (!mdetr::conv_wgrad_s2_f32_supported(d, nullptr, nullptr)) return 0;
+    return mdetr::conv_wgrad_s2_f32_chunks(d);
+}
+
+int mdetr_conv_wgrad_s2_f32(const void *x, const void *dy, float *partial, int64_t partial_floats, int B, int H, int W, int C, int OH, int OW, int N,
+                            int K, int SI, int device, void *stream)
+{
+    const char *who = "mdetr_conv_wgrad_s2_f32";
+    if (B < 0 || H < 0 || W < 0 || C <= 0 || OH < 0 || OW < 0 || N <= 0)
+        return fail(MDETR_E_ARG, "%s: bad sizes B=%d H=%d W=%d C=%d OH=%d OW=%d N=%d", who, B, H, W, C, OH, OW, N);
+    if (B == 0 || H == 0 || W == 0 || OH == 0 || OW == 0) return fail(MDETR_E_ARG, "%s: empty problem (the caller zero-fills the gradient)", who);
+    if (K != 3 || SI != 2 || OH != (H - 1) / 2 + 1 || OW != (W - 1) / 2 + 1)
+        return fail(MDETR_E_ARG, "%s: 3x3 taps at stride 2 only, output map = ((H - 1) / 2 + 1) x ((W - 1) / 2 + 1) (K=%d SI=%d, %dx%d -> %dx%d)", who, K, SI, H, W, OH, OW);
+    if (static_cast<int64_t>(B) * H * W * C >= (1ll << 29) || static_cast<int64_t>(B) * OH * OW * N >= (1ll << 29) || static_cast<int64_t>(N) * 9 * C >= (1ll << 28))
+        return fail(MDETR_E_ARG, "%s: needs operands below 2^29 elements and 9 N C below 2^28 (B=%d H=%d W=%d C=%d N=%d)", who, B, H, W, C, N);
+    if (!x || !dy || !partial) return fail(MDETR_E_ARG, "%s: null pointer", who);
+    const mdetr::ConvWgradDims d = wgrad_dims(B, H, W, C, OH, OW, N, K, SI);
+    if (!mdetr::conv_wgrad_s2_f32_supported(d, x, dy))
+        return fail(MDETR_E_ARG, "%s: needs fp32 operands, C %% 64 == 0, N %% 32 == 0, 16-byte aligned operands (C=%d N=%d)", who, C, N);
+    const int64_t need = static_cast<int64_t>(mdetr::conv_wgrad_s2_f32_chunks(d)) * N * 9 * C;
+    if (partial_floats < need) return fail(MDETR_E_ARG, "%s: partial buffer holds %lld floats, %lld needed", who, static_cast<long long>(partial_floats), static_cast<long long>(need));
+    DeviceScope dev(device);
+    if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "%s: set device %d: %s", who, device, hipGetErrorString(dev.err));
+    const hipError_t e = mdetr::conv_wgrad_s2_f32_launch(x, dy, partial, d, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MDETR_E_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+    return MDETR_OK;
+}
+
 // csrc/twgrad.hip (transposing LDS reads) unless MDETR_TUNE="twgrad=0" asks for the 1x1 case of csrc/conv_wgrad.hip (tests)
 static bool twgrad_wanted(int64_t T, int C, int N)
 {

@@ -26,4 +26,11 @@ bool conv_wgrad_f32_supported(const ConvWgradDims &d, const void *x, const void 
 int conv_wgrad_f32_chunks(const ConvWgradDims &d);
 hipError_t conv_wgrad_f32_launch(const void *x, const void *dy, float *part, const ConvWgradDims &d, hipStream_t st);
 
+// The fp32 form at stride 2 (conv_wgrad_s2_f32_kernel): x and dy fp32, K = 3, SI = 2 (OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1), DB = 0 only;
+// B H W C and B OH OW N below 2^29 elements.  The same split, the same six terms, the same partials: fp32 [chunks][N][3][3][C],
+// chunks = conv_wgrad_s2_f32_chunks(d).
+bool conv_wgrad_s2_f32_supported(const ConvWgradDims &d, const void *x, const void *dy);
+int conv_wgrad_s2_f32_chunks(const ConvWgradDims &d);
+hipError_t conv_wgrad_s2_f32_launch(const void *x, const void *dy, float *part, const ConvWgradDims &d, hipStream_t st);
+
 }  // namespace mdetr

@@ -23,7 +23,8 @@
 // into the parameter's dtype (deterministic, no atomics).
 // Algorithmic bytes = 2 B (H W C + OH OW N) + 4 TR TS N C;  flops = 2 B OH OW TR TS C N.  MFMA-bound by design.
 // The fp32 form of the 3x3 / stride-1 case (mdetr_conv_wgrad_f32: fp32 x and dy, three-way bf16 split, six terms per product) is the
-// sibling kernel conv_wgrad_f32_kernel further down.
+// sibling kernel conv_wgrad_f32_kernel further down; the fp32 form of the 3x3 / stride-2 case (mdetr_conv_wgrad_s2_f32) is
+// conv_wgrad_s2_f32_kernel behind it, with a tile of its own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -429,18 +430,203 @@ hipError_t launch_f32(const void *x, const void *dy, float *part, WgradGeom g, h
     return hipGetLastError();
 }
 
-WgradGeom geometry(const ConvWgradDims &d, int cols = kCols)
+// ---- The fp32 form at stride 2 (mdetr_conv_wgrad_s2_f32): x and dy fp32, 3 x 3 taps, stride 2, pad 1.  A sibling of conv_wgrad_f32_kernel --
+// neither kernel above has a flag for it.  The arithmetic is that kernel's: split4 once per piece, transpose8x8 per part into the part's
+// LDS plane, the six terms lo.hi hi.lo mid.mid mid.hi hi.mid hi.hi into the one accumulator of a tap column; buffer-resource loads (padding
+// and ragged tiles read as zeros), one LDS buffer with the next tile's loads in flight, the partials' layout.  What differs is the tile:
+// the X window of q output columns is 2 q + 1 column slots, stored de-interleaved (q + 1 even ones, then q odd ones) as in
+// conv_wgrad_kernel<2, 3>, and three planes of the stride-1 geometry would take 3 x (128 x 17 + 64 x 33) x 16 = 205 824 bytes.  This
+// kernel takes an 8-COLUMN pixel tile AND a 64-row n block:
+//   dYt 64 n x 9 slots, Xt 64 c x 17 slots (9 even + 8 odd), three planes: 3 x (64 x 9 + 64 x 17) x 16 = 79 872 bytes
+// -- half of the CU's 160 KB, so TWO workgroups of 4 waves share a CU and one's split / transpose (VALU, LDS stores) runs under the
+// other's matrix instructions; either choice alone (107 520 / 153 600 bytes) leaves one workgroup per CU whose waves all wait at the
+// same two barriers.  __launch_bounds__(256, 2) keeps the 256-register budget that two waves per SIMD need.
+// Workgroup = 4 waves: (tap row t, 64 n, 64 c, a chunk of 8-row x 8-column pixel tiles); wave w owns n-block w & 1 and c-block w >> 1.
+// A tile is 4 k-steps (2 columns x 8 rows).  Loading tasks, one per wave, lane = 8 piece + column: waves 0 - 2 the 17 window slots
+// x 64 channels of X (the third wave's lanes beyond slot 16 load and store nothing), wave 3 the 8 columns x 64 channels of dY.  The 8
+// lanes of a ds_write_b128 group store 8 CONSECUTIVE slots of one channel row (32 banks: conflict-free whatever the row stride); the
+// rows are 9 and 17 slots apart -- odd -- so the 16 lanes of a ds_read_b128 group (16 distinct residues of l31 mod 16) fall on 16
+// distinct slots of the 256-byte bank row.
+constexpr int kThreadsS2 = 256;
+constexpr int kNBS2 = 64, kColsS2 = 8;                                       // output channels per workgroup, columns of a pixel tile
+constexpr int kDyStrideS2 = kColsS2 + 1, kXCS2 = 2 * kColsS2 + 1, kXStrideS2 = kXCS2 | 1, kEvenS2 = kColsS2 + 1;
+constexpr int kDyPlaneS2 = kNBS2 * kDyStrideS2, kXPlaneS2 = kCB * kXStrideS2;            // 16-byte slots of one plane
+constexpr size_t kLdsS2 = static_cast<size_t>(3) * (kDyPlaneS2 + kXPlaneS2) * 16;
+static_assert(kLdsS2 == 79872 && 2 * kLdsS2 <= 160 * 1024, "three planes of the 64 x 64 tile, 8 columns: two workgroups per CU");
+static_assert(kDyStrideS2 % 2 == 1 && kXStrideS2 % 2 == 1,"odd row strides: conflict-free operand reads");
+
+__global__ __launch_bounds__(kThreadsS2, 2)
+void conv_wgrad_s2_f32_kernel(const float *__restrict__ x, const float *__restrict__ dy, float *__restrict__ part, const WgradGeom g)
+{
+    constexpr int TS = 3;
+    MDETR_DYNAMIC_LDS(unsigned char, wgrad_s2_smem);
+    bf16x8 *dyt = reinterpret_cast<bf16x8 *>(wgrad_s2_smem);                 // [3 planes][kNBS2][kDyStrideS2]
+    bf16x8 *xt = dyt + 3 * kDyPlaneS2;                                       // [3 planes][kCB][kXStrideS2]
+    const ConvWgradDims &d = g.d;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, l31 = lane & 31;
+    const int nsub = wave & 1, csub = wave >> 1;
+    int id = blockIdx.x;
+    const int chunk = id % g.chunks; id /= g.chunks;
+    const int t = id % TS; id /= TS;                                         // tap row
+    const int cblk = id % g.cblocks; const int nblk = id / g.cblocks;
+    const int n0 = nblk * kNBS2, c0 = cblk * kCB;
+
+    f32x16 acc[TS];
+#pragma unroll
+    for (int e = 0; e < TS; ++e)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[e][i] = 0.f;
+
+    constexpr int CGX = (kXCS2 + 7) / 8;                                     // waves that load X: column groups of 8 slots
+    static_assert(CGX + 1 == kThreadsS2 / 64, "one loading task per wave");
+    bf16x8 stage[16];                                                        // 16 bytes = 4 fp32 each: row i = stage[2 i], stage[2 i + 1]
+    const mdetr_rsrc xr = make_rsrc(x, static_cast<unsigned>(static_cast<int64_t>(d.B) * d.H * d.W * d.C * 4));
+    const mdetr_rsrc yr = make_rsrc(dy, static_cast<unsigned>(static_cast<int64_t>(d.B) * d.OH * d.OW * d.N * 4));
+    const int ci = lane & 7, pi = lane >> 3;
+    const bool is_x = wave < CGX;                                            // wave-uniform
+    int t_rel, t_ch, t_dst;
+    if (is_x) {
+        const int slot = 8 * wave + ci;                                      // slots [0, 9): window columns 0, 2, .. 16; [9, 17): 1, 3, .. 15
+        t_rel = slot >= kXCS2 ? -1 : (slot < kEvenS2 ? 2 * slot : 2 * (slot - kEvenS2) + 1);
+        t_ch = (c0 + pi * 8) * 4;
+        t_dst = pi * 8 * kXStrideS2 + slot;
+    } else {
+        t_rel = ci;
+        t_ch = n0 + pi * 8 < d.N ? (n0 + pi * 8) * 4 : -1;
+        t_dst = pi * 8 * kDyStrideS2 + ci;
+    }
+    auto fetch = [&](int u) {                                                // global loads of pixel tile u
+        const int ct = u % g.ctiles; u /= g.ctiles;
+        const int band = u % g.bands; const int b = u / g.bands;
+        const int r0 = band * kRows, q0 = ct * kColsS2;
+        if (is_x) {
+            const int col = 2 * q0 + t_rel - 1;
+            const bool in = t_rel >= 0 && col >= 0 && col < d.W;
+            const unsigned lane_off = in ? static_cast<unsigned>(col * d.C * 4 + t_ch) : 0u;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int row = 2 * (r0 + i) + t - 1;                        // uniform
+                const bool ok = in && row >= 0 && row < d.H;
+                const unsigned so = (row >= 0 && row < d.H) ? static_cast<unsigned>((b * d.H + row) * d.W) * static_cast<unsigned>(d.C * 4) : 0u;
+                stage[2 * i] = rsrc_load_bf16x8(xr, ok ? lane_off : kRsrcOob, so);
+                stage[2 * i + 1] = rsrc_load_bf16x8(xr, ok ? lane_off + 16u : kRsrcOob, so);
+            }
+        } else {
+            const int col = q0 + t_rel;
+            const bool in = col < d.OW && t_ch >= 0;
+            const unsigned lane_off = in ? static_cast<unsigned>(col * d.N * 4 + t_ch) : 0u;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int row = r0 + i;
+                const bool ok = in && row < d.OH;
+                const unsigned so = row < d.OH ? static_cast<unsigned>((b * d.OH + row) * d.OW) * static_cast<unsigned>(d.N * 4) : 0u;
+                stage[2 * i] = rsrc_load_bf16x8(yr, ok ? lane_off : kRsrcOob, so);
+                stage[2 * i + 1] = rsrc_load_bf16x8(yr, ok ? lane_off + 16u : kRsrcOob, so);
+            }
+        }
+    };
+    auto commit = [&]() {                                                    // split once, transpose each part's block into its plane
+        bf16x8 pl[3][8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                float f[4];
+                __builtin_memcpy(f, &stage[2 * i + s], 16);
+                bf16x4 h, m, l;
+                split4(f, h, m, l);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { pl[0][i][4 * s + j] = h[j]; pl[1][i][4 * s + j] = m[j]; pl[2][i][4 * s + j] = l[j]; }
+            }
+        }
+        if (is_x && t_rel < 0) return;                                       // (the window's 17 slots: lanes of the third group beyond them)
+        bf16x8 *dst = is_x ? xt + t_dst : dyt + t_dst;
+        const int stride = is_x ? kXStrideS2 : kDyStrideS2, plane = is_x ? kXPlaneS2 : kDyPlaneS2;
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            bf16x8 tr[8];
+            transpose8x8(pl[p], tr);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) dst[p * plane + q * stride] = tr[q];
+        }
+    };
+    auto products = [&]() {
+        const bf16x8 *ap = dyt + (nsub * 32 + l31) * kDyStrideS2 + half;
+        const bf16x8 *bp = xt + (csub * 32 + l31) * kXStrideS2 + half;
+        constexpr int term_y[6] = {2, 0, 1, 1, 0, 0}, term_x[6] = {0, 2, 1, 0, 1, 0};       // 0 hi, 1 mid, 2 lo
+#pragma unroll 2
+        for (int ks = 0; ks < kColsS2 / 2; ++ks) {
+            bf16x8 a[3], b[TS][3];                                           // this half-wave's column of the k-step: q = 2 ks + half
+#pragma unroll
+            for (int p = 0; p < 3; ++p) {
+                a[p] = ap[p * kDyPlaneS2 + 2 * ks];
+#pragma unroll
+                for (int e = 0; e < TS; ++e)                                 // window column 2 q + e: even -> slot q + e / 2, odd -> behind the even ones
+                    b[e][p] = bp[p * kXPlaneS2 + 2 * ks + ((e & 1) ? kEvenS2 : (e >> 1))];
+            }
+#pragma unroll
+            for (int k = 0; k < 6; ++k)                                      // term by term over the tap columns: every accumulator sees the order above
+#pragma unroll
+                for (int e = 0; e < TS; ++e) acc[e] = mfma_bf16(a[term_y[k]], b[e][term_x[k]], acc[e]);
+        }
+    };
+
+    // tile u's loads were issued one step before its products; one LDS buffer
+    int u = chunk;
+    if (u < g.units) fetch(u);
+    while (u < g.units) {
+        __syncthreads();                                                     // the previous tile's LDS reads are done
+        commit();
+        const int nu = u + g.chunks;
+        if (nu < g.units) fetch(nu);                                         // in flight during this tile's products
+        __syncthreads();
+        products();
+        u = nu;
+    }
+
+    // ---- epilogue: the bf16 kernel's
+    const int c = c0 + csub * 32 + l31;
+    float *pp = part + static_cast<int64_t>(chunk) * (static_cast<int64_t>(d.N) * TS * TS * d.C);
+#pragma unroll
+    for (int e = 0; e < TS; ++e)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int n = n0 + nsub * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (n < d.N) pp[((static_cast<int64_t>(n) * TS + t) * TS + e) * d.C + c] = acc[e][r];
+        }
+}
+
+hipError_t launch_s2_f32(const void *x, const void *dy, float *part, WgradGeom g, hipStream_t st)
+{
+    auto kern = conv_wgrad_s2_f32_kernel;
+    static bool attr_set[64] = {};
+    int dev_ = 0;
+    if (hipGetDevice(&dev_) != hipSuccess) dev_ = -1;
+    if (dev_ < 0 || dev_ >= 64 || !attr_set[dev_]) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 static_cast<int>(kLdsS2));
+        if (e != hipSuccess) return e;
+        if (dev_ >= 0 && dev_ < 64) attr_set[dev_] = true;
+    }
+    const int64_t blocks = static_cast<int64_t>(g.chunks) * 3 * g.cblocks * g.nblocks;
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(kThreadsS2), kLdsS2, st, static_cast<const float *>(x),
+                       static_cast<const float *>(dy), part, g);
+    return hipGetLastError();
+}
+
+// cols x nb: the pixel tile's columns and the n block of the kernel served; target: the workgroups to aim for without the tune key
+WgradGeom geometry(const ConvWgradDims &d, int cols = kCols, int nb = kNB, int target = 256)
 {
     WgradGeom g;
     g.d = d;
     g.bands = (d.OH + kRows - 1) / kRows;
     g.ctiles = (d.OW + cols - 1) / cols;
     g.units = d.B * g.bands * g.ctiles;
-    g.nblocks = (d.N + kNB - 1) / kNB;
+    g.nblocks = (d.N + nb - 1) / nb;
     g.cblocks = d.C / kCB;
-    // one workgroup per CU (104-134 KB of LDS): about 256 workgroups, each with at least one pixel tile
+    // one workgroup per CU (104-134 KB of LDS): about 256 workgroups, each with at least one pixel tile (the fp32 stride-2 form: two
+    // per CU, about 512)
     const int base = d.K * g.nblocks * g.cblocks;
-    int target = 256;
     char tune_buf[16];
     if (const char *ev = tune_str("conv_wgrad_wgs", tune_buf, sizeof(tune_buf))) {                    // A/B runs: workgroups to aim for
         const int f = atoi(ev);
@@ -495,6 +681,27 @@ hipError_t conv_wgrad_f32_launch(const void *x, const void *dy, float *part, con
                       2.0 * d.B * d.OH * d.OW * d.C * d.N * 9 / 1e6,
                       (4.0 * d.B * (static_cast<double>(d.H) * d.W * d.C + static_cast<double>(d.OH) * d.OW * d.N) + 4.0 * g.chunks * 9 * d.N * d.C) / 1e3);
     return launch_f32(x, dy, part, g, st);
+}
+
+bool conv_wgrad_s2_f32_supported(const ConvWgradDims &d, const void *x, const void *dy)
+{
+    const auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    // (sizes first: nothing below is evaluated on a problem whose 32-bit byte offsets would wrap)
+    return d.K == 3 && d.SI == 2 && d.DB == 0 && d.B > 0 && d.H > 0 && d.W > 0 && d.OH == (d.H - 1) / 2 + 1 && d.OW == (d.W - 1) / 2 + 1 &&
+           d.C > 0 && d.C % 64 == 0 && d.N > 0 && d.N % 32 == 0 && al(x) && al(dy) && static_cast<int64_t>(d.N) * 9 * d.C < (1ll << 28) &&
+           static_cast<int64_t>(d.B) * d.H * d.W * d.C < (1ll << 29) && static_cast<int64_t>(d.B) * d.OH * d.OW * d.N < (1ll << 29);
+}
+
+// (two workgroups per CU: 512 to aim for)
+int conv_wgrad_s2_f32_chunks(const ConvWgradDims &d) { return geometry(d, kColsS2, kNBS2, 512).chunks; }
+
+hipError_t conv_wgrad_s2_f32_launch(const void *x, const void *dy, float *part, const ConvWgradDims &d, hipStream_t st)
+{
+    const WgradGeom g = geometry(d, kColsS2, kNBS2, 512);
+    ProfileScope prof(9, conv_mflop(static_cast<int64_t>(d.B) * d.OH * d.OW, static_cast<int64_t>(d.C) * d.N * 9), st,
+                      2.0 * d.B * d.OH * d.OW * d.C * d.N * 9 / 1e6,
+                      (4.0 * d.B * (static_cast<double>(d.H) * d.W * d.C + static_cast<double>(d.OH) * d.OW * d.N) + 4.0 * g.chunks * 9 * d.N * d.C) / 1e3);
+    return launch_s2_f32(x, dy, part, g, st);
 }
 
 }  // namespace mdetr

@@ -3,7 +3,8 @@ library convolutions they replace (MIOpen through aten), at the shapes of the tr
 channels_last.  TFLOP/s = 2 B OH OW K K C N / t; `frac_mfma` against the 2.5 PFLOP/s dense bf16 rate.
 
     python -m monodetr_amd.tools.convbench [--iters 20] [--only wgrad|strided|stem]
-    python -m monodetr_amd.tools.convbench --dtype fp32 [--runs 3]      (the fp32 forms of conv3x3.hip / conv_wgrad.hip against the library: `fp32_rows`)
+    python -m monodetr_amd.tools.convbench --dtype fp32 [--runs 3]      (the fp32 forms of conv3x3.hip / conv_wgrad.hip against the library: `fp32_rows`;
+                                                                         the weight-gradient rows include the 3x3 / stride-2 sites, `..._s2`)
     python -m monodetr_amd.tools.convbench --dtype fp32 --only strided  (the fp32 form of conv_taps.hip on the model's stride-2 3x3 sites: `fp32_strided_rows`)
 """
 import argparse
@@ -64,6 +65,20 @@ def fp32_rows(a, dev, B):
         res["f32_wgrad_%s_library" % tag] = row(lambda i: torch.ops.aten.convolution_backward(
             dys[i], xs[i], w, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1, (False, True, False)), flops)
         res["f32_wgrad_%s_chunks" % tag] = conv_wgrad_ext._lib().mdetr_conv_wgrad_f32_chunks(B, H, W, C, H, W, C, 3, 1)
+    # the 3x3 / stride-2 sites (layer2.0 / layer3.0 / layer4.0 conv2; the depth predictor's downsample is layer3.0's problem): the
+    # stride-2 form (mdetr_conv_wgrad_s2_f32) + the sum over its chunks against the library's weight gradient at stride 2, (H, W) the INPUT
+    conv_wgrad_ext.ENABLED_CONV_S2_F32 = True
+    for tag, C, H, W in (("layer2_s2", 128, 96, 320), ("layer3_s2", 256, 48, 160), ("layer4_s2", 512, 24, 80)):
+        OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        flops = 2.0 * B * OH * OW * 9 * C * C
+        xs = [(torch.randn(B, H, W, C, device=dev) * 0.5).permute(0, 3, 1, 2) for _ in range(nsets)]
+        dys = [torch.randn(B, OH, OW, C, device=dev).permute(0, 3, 1, 2) for _ in range(nsets)]
+        w = (torch.randn(C, 3, 3, C, device=dev) / (3.0 * C ** 0.5)).permute(0, 3, 1, 2)
+        res["f32_wgrad_%s_routed_to_kernel" % tag] = bool(conv_wgrad_ext.supported_f32_s2(xs[0], dys[0]))       # (the shape rule; both are timed)
+        res["f32_wgrad_%s_kernel" % tag] = row(lambda i: conv_wgrad_ext.weight_gradient(xs[i], dys[i], 3, 2, torch.float32), flops)
+        res["f32_wgrad_%s_library" % tag] = row(lambda i: torch.ops.aten.convolution_backward(
+            dys[i], xs[i], w, None, (2, 2), (1, 1), (1, 1), False, (0, 0), 1, (False, True, False)), flops)
+        res["f32_wgrad_%s_chunks" % tag] = conv_wgrad_ext._lib().mdetr_conv_wgrad_s2_f32_chunks(B, H, W, C, OH, OW, C, 3, 2)
     return res
 
 
