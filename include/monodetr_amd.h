@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MDETR_ABI_VERSION 20
+#define MDETR_ABI_VERSION 21
 
 /* element types of the floating-point tensors */
 #define MDETR_F32 0
@@ -714,6 +714,23 @@ int mdetr_conv_dgrad_s2_f32(const void *dy, const void *wt, void *dx, int B, int
  *   y         bf16 [B, (H - 1) / 2 + 1, (W - 1) / 2 + 1, 64], 8-byte aligned
  */
 int mdetr_conv_stem(const void *x, const void *w_packed, const float *shift, void *y, int B, int H, int W, int device, void *stream);
+/*
+ * The fp32 form (ABI 21; csrc/conv_stem.hip, conv_stem_f32_kernel) for the stem of the fp32 configurations: the same convolution, shift
+ * and ReLU with x, shift and y in fp32.  Every image element is split once into three bf16 parts (hi, mid, lo) on its way into LDS, the
+ * weight arrives split (the stem is frozen: the caller splits once), and a product is six matrix-instruction terms, small ones first,
+ * into one fp32 accumulator -- fp32-accurate (what is dropped is below 2^-24 of |x||w| per product).  Deterministic, no atomics.
+ *   x         fp32 [B, H, W, 3] (a channels_last [B, 3, H, W] image batch), 4-byte aligned
+ *   w_planes  bf16 [3][64][176]: plane 0 = hi = bf16(w), plane 1 = mid = bf16(w - hi), plane 2 = lo = bf16(w - hi - mid), each in the
+ *             layout of w_packed above; every other element -- the pad columns of all three planes -- exactly zero; 16-byte aligned
+ *   shift     fp32 [64] or NULL
+ *   y         fp32 [B, (H - 1) / 2 + 1, (W - 1) / 2 + 1, 64], 16-byte aligned
+ * Negative sizes, a null x / w_planes / y, a misaligned pointer or B H W 12 >= 2^31 (32-bit byte offsets): MDETR_E_ARG with a message,
+ * judged before any pointer is dereferenced.  An empty problem returns 0 and launches nothing.
+ * An infinite pixel yields NaN (x - bf16(x)), no fix-up pass.  The pad elements of an operand group are the next pixel's channels
+ * against zero weights: a non-finite pixel at (row i, column p) also turns the outputs at column (p - 4) / 2 of the rows whose windows
+ * hold row i into NaN, beyond its 7x7 receptive field.
+ */
+int mdetr_conv_stem_f32(const void *x, const void *w_planes, const float *shift, void *y, int B, int H, int W, int device, void *stream);
 
 /*
  * Weight gradient of the 3x3 (stride 1 / 2, pad 1) and 1x1 (stride 2) convolutions on the matrix cores (csrc/conv_wgrad.hip):

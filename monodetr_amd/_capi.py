@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MDETR_LIB_PATH") or os.path.join(_HERE, "libmonodetr_
 
 MDETR_F32, MDETR_F64, MDETR_BF16 = 0, 1, 2
 MDETR_E_UNSUPPORTED = -4
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 _c_int, _c_vp = ctypes.c_int, ctypes.c_void_p
 
@@ -76,6 +76,7 @@ SIGNATURES = {
     "mdetr_conv_taps_f32_split": (_c_int, [_c_vp] * 4 + [ctypes.c_int64, _c_vp, _c_int, _c_int, _c_vp]),
     "mdetr_conv_dgrad_s2_f32": (_c_int, [_c_vp] * 3 + [_c_int] * 8 + [_c_int, _c_vp]),
     "mdetr_conv_stem": (_c_int, [_c_vp] * 4 + [_c_int] * 3 + [_c_int, _c_vp]),
+    "mdetr_conv_stem_f32": (_c_int, [_c_vp] * 4 + [_c_int] * 3 + [_c_int, _c_vp]),
     "mdetr_conv_wgrad_chunks": (_c_int, [_c_int] * 9),
     "mdetr_conv_wgrad": (_c_int, [_c_vp] * 3 + [ctypes.c_int64] + [_c_int] * 9 + [_c_int, _c_vp]),
     "mdetr_conv_wgrad_f32_chunks": (_c_int, [_c_int] * 9),

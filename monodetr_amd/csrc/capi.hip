@@ -953,6 +953,26 @@ int mdetr_conv_stem(const void *x, const void *w_packed, const float *shift, voi
     return MDETR_OK;
 }
 
+int mdetr_conv_stem_f32(const void *x, const void *w_planes, const float *shift, void *y, int B, int H, int W, int device, void *stream)
+{
+    const char *who = "mdetr_conv_stem_f32";
+    if (B < 0 || H < 0 || W < 0) return fail(MDETR_E_ARG, "%s: bad sizes B=%d H=%d W=%d", who, B, H, W);
+    if (B == 0 || H == 0 || W == 0) return MDETR_OK;
+    if (!x || !w_planes || !y) return fail(MDETR_E_ARG, "%s: null pointer", who);
+    const auto al = [](const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
+    if (!al(w_planes, 16)) return fail(MDETR_E_ARG, "%s: the packed weight planes are not 16-byte aligned", who);
+    if (!al(y, 16)) return fail(MDETR_E_ARG, "%s: y is not 16-byte aligned", who);
+    if (!al(x, 4)) return fail(MDETR_E_ARG, "%s: x is not 4-byte aligned", who);
+    if (static_cast<int64_t>(B) * H * W * 12 >= (1ll << 31))
+        return fail(MDETR_E_ARG, "%s: needs an image batch below 2 GiB (B H W 12 = %lld bytes)", who, static_cast<long long>(B) * H * W * 12);
+    if (!mdetr::conv_stem_f32_supported(B, H, W, x, w_planes, y)) return fail(MDETR_E_ARG, "%s: unsupported arguments", who);
+    DeviceScope dev(device);
+    if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "%s: set device %d: %s", who, device, hipGetErrorString(dev.err));
+    const hipError_t e = mdetr::conv_stem_f32_launch(x, w_planes, shift, y, B, H, W, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MDETR_E_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+    return MDETR_OK;
+}
+
 static mdetr::ConvWgradDims wgrad_dims(int B, int H, int W, int C, int OH, int OW, int N, int K, int SI)
 {
     mdetr::ConvWgradDims d;

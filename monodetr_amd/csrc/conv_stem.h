@@ -10,4 +10,9 @@ namespace mdetr {
 bool conv_stem_supported(int B, int H, int W, const void *x, const void *wp, const void *y);
 hipError_t conv_stem_launch(const void *x, const void *wp, const float *shift, void *y, int B, int H, int W, hipStream_t st);
 
+// The fp32 form (conv_stem_f32_kernel): x [B, H, W, 3] fp32, wp: three packed bf16 planes [3][64][176] (hi, mid, lo of the fp32 weight, each
+// in the layout above), shift fp32 [64] or null, y [B, OH, OW, 64] fp32, 16-byte aligned; B H W 12 < 2^31 (32-bit byte offsets)
+bool conv_stem_f32_supported(int B, int H, int W, const void *x, const void *wp, const void *y);
+hipError_t conv_stem_f32_launch(const void *x, const void *wp, const float *shift, void *y, int B, int H, int W, hipStream_t st);
+
 }  // namespace mdetr

@@ -14,7 +14,7 @@ AUTOTUNE_SWITCHES = ("MDETR_FUSED_LOSSES", "MDETR_FUSED_ADAMW", "MDETR_MSDA_PROL
                      "MDETR_FUSED_EPILOGUE", "MDETR_GEMM_RELU", "MDETR_CONV3X3", "MDETR_GROUP_NORM", "MDETR_SMALL_WGRAD",
                      "MDETR_CONV_STRIDED", "MDETR_CONV_WGRAD", "MDETR_CONV_STEM", "MDETR_TGEMM", "MDETR_WFOLD", "MDETR_RELU_PREMASK",
                      "MDETR_HEADS", "MDETR_CHUNK_SUMS", "MDETR_HEAD_TAIL", "MDETR_TGEMM_F32", "MDETR_TWGRAD_F32",
-                     "MDETR_CONV3X3_F32", "MDETR_CONV_WGRAD_F32", "MDETR_CONV_STRIDED_F32", "MDETR_PARAM_PACK",
+                     "MDETR_CONV3X3_F32", "MDETR_CONV_WGRAD_F32", "MDETR_CONV_STRIDED_F32", "MDETR_CONV_STEM_F32", "MDETR_PARAM_PACK",
                      "MDETR_CONV_WGRAD_S2_F32")
 ALL_SWITCHES = AUTOTUNE_SWITCHES
 # The measured configuration.  family -> the GPU tests that hold it to the default path / the framework operators
@@ -40,6 +40,7 @@ SWITCH_TESTS = {
     "MDETR_CONV_WGRAD_F32": "test_conv_wgrad_f32_gpu.py::test_conv_wgrad_f32_*, test_conv_wgrad_f32_gpu.py::test_fp32_stage_with_the_conv_wgrad_switch_*",
     "MDETR_CONV_STRIDED_F32": "test_conv_strided_f32_gpu.py::test_conv_strided_f32_*, test_conv_strided_f32_gpu.py::test_fp32_stage_with_the_conv_strided_switch_*",
     "MDETR_CONV_WGRAD_S2_F32": "test_conv_wgrad_s2_f32_gpu.py::test_conv_wgrad_s2_f32_*, test_conv_wgrad_s2_f32_gpu.py::test_fp32_stage_with_the_conv_wgrad_s2_switch_*",
+    "MDETR_CONV_STEM_F32": "test_conv_stem_f32_gpu.py::test_conv_stem_f32_*, test_conv_stem_f32_gpu.py::test_fp32_stem_with_the_switch_*",
     "MDETR_RELU_PREMASK": "test_tgemm_gpu.py::test_masked_input_gradient_*, test_tgemm_gpu.py::test_bottleneck_stage_with_premasked_relu_*, test_exact_products_gpu.py::test_exact_tgemm_masked_*",
     "MDETR_HEADS": "test_sgemm_gpu.py::test_sgemm_*, test_sgemm_gpu.py::test_heads_level_*, test_training_step_with_the_grouped_heads_*, test_exact_products_gpu.py::test_exact_sgemm_grouped_*",
     "MDETR_HEAD_TAIL": "test_sgemm_gpu.py::test_head_tail_*, test_sgemm_gpu.py::test_training_step_with_the_head_tail_*, test_head_tail_cases_gpu.py::test_head_tail_*",
@@ -77,6 +78,9 @@ COMMITTED_SWITCHES = {
     # MDETR_CONV_WGRAD_S2_F32: the weight gradient of the same fp32 stride-2 convolutions through conv_wgrad_s2_f32_kernel of
     # csrc/conv_wgrad.hip (mdetr_conv_wgrad_s2_f32); consulted in conv_taps_ext._ConvStrided.backward only, so it acts together with
     # MDETR_CONV_STRIDED_F32.  Opt-in: on NO committed list; DESIGN.md 3.5 records what was measured.
+    # MDETR_CONV_STEM_F32: the frozen 7x7 / stride-2 stem of the fp32 configurations with its shift and ReLU through conv_stem_f32_kernel
+    # of csrc/conv_stem.hip (mdetr_conv_stem_f32) instead of the library's convolution and a bias_act pass.  Opt-in: on NO committed
+    # list; DESIGN.md 3.5 records what was measured.
     # MDETR_PARAM_PACK: the transformer's packed / summed projection parameters of a forward pass from one launch and the encoder's
     # level positions as one [S, C] tensor from one more (csrc/wpack.hip), bit-identical; DESIGN.md 3.7 records the launches and the step.
     "bf16": ("MDETR_FUSED_LOSSES", "MDETR_FUSED_ADAMW", "MDETR_FUSED_LN", "MDETR_MSDA_PROLOGUE", "MDETR_MSDA_BF16",
@@ -131,6 +135,7 @@ def apply_switches(names):
     conv_wgrad_ext.ENABLED_CONV_F32 = "MDETR_CONV_WGRAD_F32" in names
     conv_wgrad_ext.ENABLED_CONV_S2_F32 = "MDETR_CONV_WGRAD_S2_F32" in names
     conv_stem_ext.ENABLED = "MDETR_CONV_STEM" in names
+    conv_stem_ext.ENABLED_F32 = "MDETR_CONV_STEM_F32" in names
     group_norm_ext.ENABLED = "MDETR_GROUP_NORM" in names
     small_wgrad_ext.ENABLED = "MDETR_SMALL_WGRAD" in names
     ms_deform_attn_func._NATIVE_BF16 = "MDETR_MSDA_BF16" in names

@@ -228,6 +228,9 @@ def conv_bn(x, conv, bn, relu, skip_out=False, relu_token=None, hand_out_token=F
             x = pointwise_conv(x, w, b)
         elif relu and conv_stem_ext.ENABLED and conv_stem_ext.supported(x, w, conv.stride, conv.padding, conv.dilation, conv.groups):
             return conv_stem_ext.conv_stem(x, w, shift)              # the frozen 7x7 / stride-2 stem (csrc/conv_stem.hip), shift + ReLU inside
+        elif relu and conv_stem_ext.ENABLED_F32 and not torch.is_autocast_enabled() and not conv_taps_ext._autocast(x) \
+                and conv_stem_ext.supported_f32(x, w, conv.stride, conv.padding, conv.dilation, conv.groups):
+            return conv_stem_ext.conv_stem(x, w, shift)              # the same in fp32 (mdetr_conv_stem_f32: three-way bf16 split)
         elif conv_taps_ext.ENABLED and conv_taps_ext.supported(x, w, conv.stride, conv.padding, conv.dilation, conv.groups):
             # the stride-2 3x3 of a stage's first block and its 1x1 / stride-2 projection shortcut (csrc/conv_taps.hip), forward,
             # input gradient (four pixel-parity classes) and weight gradient (csrc/conv_wgrad.hip) by hand

@@ -6,6 +6,7 @@ channels_last.  TFLOP/s = 2 B OH OW K K C N / t; `frac_mfma` against the 2.5 PFL
     python -m monodetr_amd.tools.convbench --dtype fp32 [--runs 3]      (the fp32 forms of conv3x3.hip / conv_wgrad.hip against the library: `fp32_rows`;
                                                                          the weight-gradient rows include the 3x3 / stride-2 sites, `..._s2`)
     python -m monodetr_amd.tools.convbench --dtype fp32 --only strided  (the fp32 form of conv_taps.hip on the model's stride-2 3x3 sites: `fp32_strided_rows`)
+    python -m monodetr_amd.tools.convbench --dtype fp32 --only stem     (the fp32 form of conv_stem.hip against the library convolution + the shift / ReLU pass: `fp32_stem_rows`)
 """
 import argparse
 import json
@@ -171,6 +172,40 @@ def fp32_strided_rows(a, dev, B):
     return res
 
 
+def fp32_stem_rows(a, dev, B, sizes=((384, 1280), (512, 1760))):
+    """--dtype fp32 --only stem: the fp32 form of csrc/conv_stem.hip (mdetr_conv_stem_f32: convolution, shift and ReLU in one launch) against
+    the library route of backbone.conv_bn on the same fp32 operands -- F.conv2d, then bias_act_ext.bias_act(..., relu=True) --, at the image
+    sizes of the two fp32 configurations, by the method of `fp32_rows`."""
+    import statistics
+    from monodetr_amd import bias_act_ext, conv_stem_ext
+    from .gemmbench import graph_time
+    conv_stem_ext.ENABLED_F32 = True
+    res, nsets, reps = {}, 2, max(4, a.iters)
+
+    def row(f, flops):
+        us = sorted(graph_time(f, nsets, reps) for _ in range(a.runs))
+        med = statistics.median(us)
+        return dict(us=round(med, 2), spread_us=[us[0], us[-1]], TFLOPs=round(flops / med / 1e6, 1), frac_six_term_mfma=round(6.0 * flops / (med * 1e-6) / 2.5e15, 4))
+
+    for H, W in sizes:
+        tag = "%dx%d" % (H, W)
+        OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        flops = 2.0 * B * OH * OW * 64 * 147
+        xs = [torch.randn(B, H, W, 3, device=dev).permute(0, 3, 1, 2) for _ in range(nsets)]
+        w = (torch.randn(64, 7, 7, 3, device=dev) / 12.0).permute(0, 3, 1, 2)
+        sh = torch.randn(64, device=dev) * 0.3
+        assert conv_stem_ext.supported_f32(xs[0], w)
+        planes = conv_stem_ext.pack_weight_f32(w)
+        y = F.conv2d(xs[0], w, None, stride=2, padding=3)
+        assert bias_act_ext.supported(y, sh)                               # (the pass conv_bn runs behind the library convolution in fp32)
+        res["f32_stem_%s_kernel" % tag] = row(lambda i: conv_stem_ext._launch_f32(xs[i], planes, sh, True), flops)
+        res["f32_stem_%s_library" % tag] = row(lambda i: bias_act_ext.bias_act(F.conv2d(xs[i], w, None, stride=2, padding=3), sh, None, relu=True), flops)
+        res["f32_stem_%s_library_conv_alone" % tag] = row(lambda i: F.conv2d(xs[i], w, None, stride=2, padding=3), flops)
+        k, lib = res["f32_stem_%s_kernel" % tag], res["f32_stem_%s_library" % tag]
+        res["f32_stem_%s_kernel_ahead" % tag] = bool(k["us"] < lib["spread_us"][0])      # the median ahead of the library route's own [min, max]
+    return res
+
+
 class _no_split:
     """MDETR_TUNE conv_taps_split=0 for the duration of a block (the unsplit forward of a site the route would split)."""
 
@@ -198,7 +233,7 @@ def main():
     dev, B = "cuda", a.batch
     from monodetr_amd import conv3x3_ext, conv_taps_ext, conv_wgrad_ext
     if a.dtype == "fp32":
-        print(json.dumps(fp32_strided_rows(a, dev, B) if a.only == "strided" else fp32_rows(a, dev, B)))
+        print(json.dumps(fp32_strided_rows(a, dev, B) if a.only == "strided" else fp32_stem_rows(a, dev, B) if a.only == "stem" else fp32_rows(a, dev, B)))
         return
     conv_wgrad_ext.ENABLED = True
     res = {}
