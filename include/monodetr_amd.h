@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MDETR_ABI_VERSION 21
+#define MDETR_ABI_VERSION 22
 
 /* element types of the floating-point tensors */
 #define MDETR_F32 0
@@ -931,6 +931,29 @@ int mdetr_group_norm_backward(int io_dtype, int param_dtype, const void *dy, con
 int mdetr_lsa_forward(const float *cost, const int32_t *num_targets, int32_t *assign,
                       int layers, int images, int groups, int n, int kmax,
                       int64_t img_stride, int64_t q_stride, int64_t t_stride, int device, void *stream);
+
+/*
+ * Head outputs -> finished KITTI detections in one launch (ABI 22; csrc/detect.hip, arithmetic in csrc/detect_math.h): the top-k
+ * selection of helpers/decode_helper.py's extract_dets_from_outputs and the per-detection decoding of its decode_detections
+ * (reference lib/helpers/decode_helper.py:8-110), one workgroup per image.
+ *   logits [B, Q, C], boxes [B, Q, 6] (cx cy l r t b), angle [B, Q, 24], dim3d [B, Q, 3], depth [B, Q, 2] (depth, log variance): fp32, dense
+ *   calib [B, 6] (cu cv fu fv tx ty of the frame), img_size [B, 2] (W H), cls_mean_size [C, 3]: fp64
+ *   rows  [B, topk, 14] fp64: rank j of image b as [class, alpha, x1, y1, x2, y2, h, w, l, x, y, z, ry, score * sigma], computed in fp64
+ *         from the fp32 record as numpy >= 2 computes decode_detections; every rank is written, kept or not
+ *   keep  [B, topk] uint8: 1 iff the record's score >= (float)threshold, compared in fp32
+ *   dets37 [B, topk, 37] fp32 or NULL: the record of extract_dets_from_outputs, fp32 operation by operation (score and sigma through
+ *         expf: within a few units of 6e-8 of the framework's, the other 35 columns bit for bit)
+ * Rank order is by LOGIT: NaN first (as torch.topk places it; its score is NaN and it is never kept), then descending value with
+ * -0 == +0, equal values by ascending flat index q * C + c.  That is torch.topk(sigmoid(logits)) wherever it is well defined, and
+ * the rule where it is not (equal scores).  Deterministic; plain stores, no atomics, no workspace.
+ * Limits: 1 <= topk <= Q * C <= 8192, C >= 1, B >= 0; anything else MDETR_E_ARG, a pointer not aligned to its element MDETR_E_ALIGN,
+ * both judged before any pointer is dereferenced.  B == 0 returns 0, launches nothing and looks at no pointer.
+ * device == -1: every pointer is HOST memory and the same arithmetic runs serially on the calling thread behind a stable sort
+ * (`stream` ignored) -- the form the CPU tests and CPU tensors take.
+ */
+int mdetr_detect_decode(const float *logits, const float *boxes, const float *angle, const float *dim3d, const float *depth, const double *calib,
+                        const double *img_size, const double *cls_mean_size, int B, int Q, int C, int topk, double threshold, double *rows,
+                        uint8_t *keep, float *dets37, int device, void *stream);
 
 /*
  * Optional per-launch kernel timing with HIP events recorded on the launch stream (bench.py's

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MDETR_LIB_PATH") or os.path.join(_HERE, "libmonodetr_
 
 MDETR_F32, MDETR_F64, MDETR_BF16 = 0, 1, 2
 MDETR_E_UNSUPPORTED = -4
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _c_int, _c_vp = ctypes.c_int, ctypes.c_void_p
 
@@ -107,6 +107,7 @@ SIGNATURES = {
     "mdetr_unfold_grads": (_c_int, [_c_int] + [_c_vp] * 6 + [_c_int, _c_vp]),
     "mdetr_pack_params": (_c_int, [_c_vp, _c_int, _c_int, _c_vp]),
     "mdetr_level_pos": (_c_int, [_c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_int, _c_vp, _c_int, _c_int, _c_int, _c_vp]),
+    "mdetr_detect_decode": (_c_int, [_c_vp] * 8 + [_c_int] * 4 + [ctypes.c_double] + [_c_vp] * 3 + [_c_int, _c_vp]),
     "mdetr_maxpool3x3s2_bf16": (_c_int, [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_vp]),
     "mdetr_decimate2": (_c_int, [_c_int, _c_vp, _c_vp, _c_int, _c_int, _c_int, ctypes.c_int64, _c_int, _c_vp]),
     "mdetr_msda_prologue_forward_packed": (_c_int, [_c_int, _c_int] + [_c_vp] * 5 + [_c_int] * 6 + [ctypes.c_int64] * 3 + [_c_int, _c_vp]),

@@ -18,8 +18,8 @@ LIB = os.path.join(HERE, "libmonodetr_amd.so")
 ARCH = "gfx950"
 
 
-# .hip files that another translation unit includes (wpack.hip: part of capi.hip, ABI 19): dependencies, not sources
-INCLUDED = [os.path.join(CSRC, "wpack.hip")]
+# .hip files that another translation unit includes (wpack.hip, ABI 19, and detect.hip, ABI 22: parts of capi.hip): dependencies, not sources
+INCLUDED = [os.path.join(CSRC, "wpack.hip"), os.path.join(CSRC, "detect.hip")]
 
 
 def sources():

@@ -38,6 +38,7 @@
 #include "msda_prologue.h"
 #include "msda_prologue_math.h"
 #include "wpack.hip"      // the parameter-packing kernels and their launchers are part of THIS translation unit (see the file's head)
+#include "detect.hip"     // likewise the detection decoder (ABI 22)
 
 namespace {
 
@@ -1290,6 +1291,36 @@ int mdetr_level_pos(const void *sine, int sine_dtype, const void *level_embed, i
     const hipError_t e = mdetr::level_pos_launch(sine, sine_dtype == MDETR_BF16, level_embed, embed_dtype == MDETR_BF16, out, out_dtype == MDETR_BF16, counts, levels, C,
                                                  static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(MDETR_E_HIP, "mdetr_level_pos: launch failed: %s", hipGetErrorString(e));
+    return MDETR_OK;
+}
+
+int mdetr_detect_decode(const float *logits, const float *boxes, const float *angle, const float *dim3d, const float *depth, const double *calib,
+                        const double *img_size, const double *cls_mean_size, int B, int Q, int C, int topk, double threshold, double *rows,
+                        uint8_t *keep, float *dets37, int device, void *stream)
+{
+    if (B < 0 || Q < 1 || C < 1 || static_cast<int64_t>(Q) * C > mdetr::kDetectMaxKeys)
+        return fail(MDETR_E_ARG, "mdetr_detect_decode: B=%d Q=%d C=%d (B >= 0, Q >= 1, C >= 1, Q * C <= %d)", B, Q, C, mdetr::kDetectMaxKeys);
+    if (topk < 1 || topk > Q * C) return fail(MDETR_E_ARG, "mdetr_detect_decode: topk=%d (1 .. Q * C = %d)", topk, Q * C);
+    if (device < -1) return fail(MDETR_E_ARG, "mdetr_detect_decode: device %d (an ordinal, or -1 for host memory)", device);
+    if (B == 0) return MDETR_OK;
+    if (!logits || !boxes || !angle || !dim3d || !depth || !calib || !img_size || !cls_mean_size || !rows || !keep)
+        return fail(MDETR_E_ARG, "mdetr_detect_decode: null pointer");
+    const uintptr_t f32 = reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(angle) |
+                          reinterpret_cast<uintptr_t>(dim3d) | reinterpret_cast<uintptr_t>(depth) | reinterpret_cast<uintptr_t>(dets37);
+    const uintptr_t f64 = reinterpret_cast<uintptr_t>(calib) | reinterpret_cast<uintptr_t>(img_size) | reinterpret_cast<uintptr_t>(cls_mean_size) |
+                          reinterpret_cast<uintptr_t>(rows);
+    if ((f32 & 3u) || (f64 & 7u)) return fail(MDETR_E_ALIGN, "mdetr_detect_decode: pointer not aligned to its element");
+    mdetr::DetectArgs a;
+    a.logits = logits; a.boxes = boxes; a.angle = angle; a.dim = dim3d; a.depth = depth; a.calib = calib; a.size = img_size; a.mean = cls_mean_size;
+    a.rows = rows; a.keep = keep; a.recs = dets37; a.B = B; a.Q = Q; a.C = C; a.topk = topk; a.threshold = static_cast<float>(threshold);
+    if (device == -1) {
+        mdetr::detect_decode_host(a);
+        return MDETR_OK;
+    }
+    DeviceScope dev(device);
+    if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "mdetr_detect_decode: set device %d: %s", device, hipGetErrorString(dev.err));
+    const hipError_t e = mdetr::detect_decode_launch(a, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MDETR_E_HIP, "mdetr_detect_decode: launch failed: %s", hipGetErrorString(e));
     return MDETR_OK;
 }
 

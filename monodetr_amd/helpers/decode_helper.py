@@ -2,7 +2,8 @@
 calls; the heat-map helpers of that file belong to centre-net style heads and are not mirrored).
 
 ``extract_dets_from_outputs`` runs on the device without host synchronisation; ``decode_detections`` is the
-reference's numpy step (image-plane decoding, back-projection with the frame's calibration), vectorised per image."""
+reference's numpy step (image-plane decoding, back-projection with the frame's calibration), vectorised per image.
+``decode_batch`` is both steps as one kernel launch and one copy to the host (``detect_ext``; opt-in, see ``Tester._detect``)."""
 import numpy as np
 import torch
 
@@ -55,5 +56,31 @@ def decode_detections(dets, info, calibs, cls_mean_size, threshold):
             ry = calibs[i].alpha2ry(alpha, x[j])
             preds.append([int(cls_id[j]), alpha, x[j] - w[j] / 2, y[j] - h[j] / 2, x[j] + w[j] / 2, y[j] + h[j] / 2]
                          + dims[j].tolist() + loc[j].tolist() + [ry, d[j, 1] * d[j, -1]])
+        results[info['img_id'][i]] = preds
+    return results
+
+
+def decode_batch(outputs, info, calibs, cls_mean_size, threshold, topk):
+    """``extract_dets_from_outputs`` + ``decode_detections`` on the device: one launch of ``mdetr_detect_decode``, one copy of the
+    result rows and keep flags to the host, no per-detection Python.  Same arguments as ``decode_detections`` with the head
+    ``outputs`` in place of ``dets``; same ``{img_id: [[cls, alpha, ...], ...]}`` result.  The calibration scalars are read from the
+    ``Calibration`` objects, so both paths see identical numbers."""
+    from .. import detect_ext
+    B = outputs['pred_logits'].shape[0]
+    mean = np.asarray(cls_mean_size, dtype=np.float64)
+    consts = np.empty(B * 8 + mean.size, dtype=np.float64)          # calibration, image sizes, mean sizes: one copy to the device
+    consts[:B * 6] = [float(v) for c in calibs for v in (c.cu, c.cv, c.fu, c.fv, c.tx, c.ty)]
+    consts[B * 6:B * 8] = np.asarray(info['img_size'], dtype=np.float64).reshape(-1)
+    consts[B * 8:] = mean.reshape(-1)
+    dev = torch.from_numpy(consts).to(outputs['pred_logits'].device)
+    found = detect_ext.detect_decode(outputs, dev[:B * 6].view(B, 6), dev[B * 6:B * 8].view(B, 2), dev[B * 8:].view(mean.shape), threshold, topk)
+    host = found.packed.cpu().numpy()
+    slots = B * topk
+    rows, keep = host[:slots * 14 * 8].view(np.float64).reshape(B, topk, 14), host[slots * 14 * 8:].view(np.bool_).reshape(B, topk)
+    results = {}
+    for i in range(B):
+        preds = rows[i][keep[i]].tolist()
+        for p in preds:
+            p[0] = int(p[0])
         results[info['img_id'][i]] = preds
     return results

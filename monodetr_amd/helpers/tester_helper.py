@@ -4,6 +4,8 @@
 Where the work happens here: the loader is this package's ``DeviceLoader`` (``inputs`` arrive on the GPU), detections
 are extracted on the device without host synchronisation (``decode_helper.extract_dets_from_outputs``), and the
 evaluation runs through ``datasets/kitti/kitti_eval_python`` (rotated overlaps on the device, statistics native).
+One more key than the reference's yaml: ``decode: device`` turns extraction and decoding into one kernel launch
+(``decode_helper.decode_batch``); the default, ``host``, is the reference's two steps.
 """
 import os
 import time
@@ -48,6 +50,14 @@ class Tester(object):
             self.evaluate()
 
     # ---- detections ---------------------------------------------------------------------------------
+    def _device_decode(self, outputs):
+        """``decode: device`` in the tester's configuration or MDETR_DETECT_DECODE=1, and head outputs the kernel takes (fp32, within
+        its limits): selection and decoding in one launch (``decode_helper.decode_batch``).  The default is the host path."""
+        if self.cfg.get('decode', 'host') != 'device' and os.environ.get('MDETR_DETECT_DECODE') != '1':
+            return False
+        from .. import detect_ext
+        return detect_ext.supported(outputs)
+
     def _detect(self, batch):
         """One batch -> ({image id: detections}, seconds spent in the model)."""
         inputs, calibs, targets, info = batch
@@ -58,6 +68,12 @@ class Tester(object):
         started = time.time()
         outputs = self.model(inputs, calibs, targets, info['img_size'].to(self.device), dn_args=0)
         spent = time.time() - started
+        if self._device_decode(outputs):
+            host_info = {key: val.detach().cpu().numpy() for key, val in info.items()}
+            frame_calibs = [dataset.get_calib(int(index)) for index in host_info['img_id']]
+            found = decode_helper.decode_batch(outputs=outputs, info=host_info, calibs=frame_calibs, cls_mean_size=dataset.cls_mean_size,
+                                               threshold=self.cfg.get('threshold', 0.2), topk=self.cfg['topk'])
+            return found, spent
         dets = decode_helper.extract_dets_from_outputs(outputs=outputs, K=self.max_objs, topk=self.cfg['topk'])
         host_info = {key: val.detach().cpu().numpy() for key, val in info.items()}
         frame_calibs = [dataset.get_calib(int(index)) for index in host_info['img_id']]
