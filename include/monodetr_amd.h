@@ -781,6 +781,24 @@ int mdetr_token_wgrad(const void *x, const void *dy, float *partial, int64_t par
                       int device, void *stream);
 
 /*
+ * Several of these problems in one call (added under ABI 22: a new entry, nothing existing changes, and tests/test_detect_capi_cpu.py
+ * holds the number at 22 -- a caller that needs the entry looks it up by name): every job is validated and planned as a call of mdetr_token_wgrad of its own --
+ * the same mdetr_token_wgrad_chunks(T, K, N) partials in the same layout with the same bits -- and the jobs of one kernel
+ * instantiation travel in ONE launch (32 jobs at most per launch).  The weight gradients of a few thousand token rows are almost all
+ * launch boundary; nothing waits for them inside a backward pass, so they are collected and sent together (chunk_sums.py).
+ *   part_elems   floats available at `part`;  K = the columns of x (C above)
+ * An error in any job fails the call before anything is launched.  (MDETR_TUNE="twgrad=0", tests: the jobs go through
+ * mdetr_token_wgrad one by one.)
+ */
+typedef struct {
+    const void *x, *dy;
+    float *part;
+    int64_t part_elems, T;
+    int32_t K, N, with_bias, pad_;
+} mdetr_twgrad_job;
+int mdetr_token_wgrad_grouped(const mdetr_twgrad_job *jobs, int njobs, int device, void *stream);
+
+/*
  * The same two gradients with x, dy and the partials in fp32 (ABI 14; csrc/twgrad.hip's fp32 form): every operand element is split
  * once into three bf16 parts (hi, mid, lo) on its way into LDS and a product is six matrix-instruction terms into fp32 accumulators,
  * db three ones-products -- fp32-accurate (what is dropped is below 2^-24 of |dy||x| per product).  Same partial layout and

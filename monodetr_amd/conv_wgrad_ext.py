@@ -102,6 +102,10 @@ ENABLED_CONV_F32 = os.environ.get("MDETR_CONV_WGRAD_F32") == "1"
 # conv_taps_ext._ConvStrided.backward only, so in the step it acts together with MDETR_CONV_STRIDED_F32.  A family of its own, opt-in,
 # on no committed list.
 ENABLED_CONV_S2_F32 = os.environ.get("MDETR_CONV_WGRAD_S2_F32") == "1"
+# MDETR_TWGRAD_GROUPED=1: inside chunk_sums.deferred() the bf16 token weight gradients of at most small_wgrad_ext.MAX_ROWS rows are
+# registered and launched together at the next flush (mdetr_token_wgrad_grouped: one launch per kernel instantiation), ahead of the
+# chunk sums that read their partials -- the same partials, bit for bit.  kernel_families decides; DESIGN.md 3.4.
+GROUPED = os.environ.get("MDETR_TWGRAD_GROUPED") == "1"
 
 
 def _chunk_sum_route(chunk_sums, cuda, cols, dtype):
@@ -137,10 +141,15 @@ def token_weight_gradient(x2, dy2, dtype, bias=False):
         part = W_.get("conv_wgrad", x2.device, chunks * cols * 4).view(torch.float32)[:chunks * cols]
     else:                                            # (a deferred sum reads its partials later: they get a buffer of their own)
         part = torch.empty(chunks * cols, dtype=torch.float32, device=x2.device)
-    rc = getattr(lib, entry)(x2.data_ptr(), dy2.data_ptr(), part.data_ptr(), part.numel(), T, K, N, 1 if bias else 0,
-                             x2.device.index if cuda else -1, torch.cuda.current_stream(x2.device).cuda_stream if cuda else None)
-    if rc != 0:
-        _capi.check(rc, entry)
+    from .small_wgrad_ext import MAX_ROWS
+    if GROUPED and batched and x2.dtype == torch.bfloat16 and T <= MAX_ROWS and chunk_sums.deferring_producers():
+        # a short token axis: the launch is nearly all boundary and nothing waits for it -- it goes out with the next flush, grouped
+        chunk_sums.register_producer(x2, dy2, part, bias)
+    else:
+        rc = getattr(lib, entry)(x2.data_ptr(), dy2.data_ptr(), part.data_ptr(), part.numel(), T, K, N, 1 if bias else 0,
+                                 x2.device.index if cuda else -1, torch.cuda.current_stream(x2.device).cuda_stream if cuda else None)
+        if rc != 0:
+            _capi.check(rc, entry)
     part = part.view(chunks, cols)
     if batched:
         both = chunk_sums.chunk_sum(part, dtype)     # one launch for all the iteration's weight gradients (chunk_sums.flush)

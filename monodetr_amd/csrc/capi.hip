@@ -1122,6 +1122,43 @@ int mdetr_token_wgrad(const void *x, const void *dy, float *partial, int64_t par
     return MDETR_OK;
 }
 
+// Several mdetr_token_wgrad problems in one call (added under ABI 22: the number is unchanged, see the header): every job validated as the single entry validates it, then ONE launch per
+// kernel instantiation and per 32 jobs (mdetr::twgrad_grouped_launch); a job the kernel does not take fails the call before anything is
+// launched.  Under MDETR_TUNE="twgrad=0" the jobs go through the single entry one by one: same checks, same kernel as there.
+int mdetr_token_wgrad_grouped(const mdetr_twgrad_job *jobs, int njobs, int device, void *stream)
+{
+    if (njobs < 0 || (njobs > 0 && !jobs)) return fail(MDETR_E_ARG, "mdetr_token_wgrad_grouped: no jobs (%d jobs)", njobs);
+    if (njobs == 0) return MDETR_OK;
+    for (int i = 0; i < njobs; ++i)
+        if (!jobs[i].x || !jobs[i].dy || !jobs[i].part) return fail(MDETR_E_ARG, "mdetr_token_wgrad_grouped: null pointer (job %d)", i);
+    if (!twgrad_wanted(8, 8, 8)) {                               // MDETR_TUNE="twgrad=0" (tests): the other kernel, job by job
+        for (int i = 0; i < njobs; ++i) {
+            const mdetr_twgrad_job &q = jobs[i];
+            const int rc = mdetr_token_wgrad(q.x, q.dy, q.part, q.part_elems, q.T, q.K, q.N, q.with_bias, device, stream);
+            if (rc != MDETR_OK) return rc;
+        }
+        return MDETR_OK;
+    }
+    std::vector<mdetr::TwgradJob> tj(static_cast<size_t>(njobs));
+    for (int i = 0; i < njobs; ++i) {
+        const mdetr_twgrad_job &q = jobs[i];
+        if (!mdetr::twgrad_supported(q.T, q.K, q.N, q.K, q.N, q.x, q.dy))
+            return fail(MDETR_E_ARG, "mdetr_token_wgrad_grouped: job %d needs C %% 8 == 0, N %% 8 == 0, 16-byte aligned operands below 2^31 bytes (T=%lld C=%d N=%d)",
+                        i, static_cast<long long>(q.T), q.K, q.N);
+        const int64_t need = static_cast<int64_t>(mdetr::twgrad_chunks(q.T, q.K, q.N)) * (static_cast<int64_t>(q.N) * q.K + (q.with_bias ? q.N : 0));
+        if (q.part_elems < need)
+            return fail(MDETR_E_ARG, "mdetr_token_wgrad_grouped: job %d: partial buffer holds %lld floats, %lld needed", i, static_cast<long long>(q.part_elems),
+                        static_cast<long long>(need));
+        mdetr::TwgradJob &t = tj[static_cast<size_t>(i)];
+        t.x = q.x; t.dy = q.dy; t.part = q.part; t.T = q.T; t.C = q.K; t.N = q.N; t.with_db = q.with_bias != 0;
+    }
+    DeviceScope dev(device);
+    if (dev.err != hipSuccess) return fail(MDETR_E_HIP, "mdetr_token_wgrad_grouped: set device %d: %s", device, hipGetErrorString(dev.err));
+    const hipError_t e = mdetr::twgrad_grouped_launch(tj.data(), njobs, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return fail(MDETR_E_HIP, "mdetr_token_wgrad_grouped: launch failed: %s", hipGetErrorString(e));
+    return MDETR_OK;
+}
+
 // The fp32 form of csrc/twgrad.hip (three-way bf16 split, six terms per product).  No twgrad=0 fallback: csrc/conv_wgrad.hip is bf16-only.
 int mdetr_token_wgrad_f32_chunks(int64_t T, int C, int N)
 {

@@ -50,6 +50,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <vector>
+
 #include <mdetr_wave.h>
 
 #include "mdetr_split.h"
@@ -87,9 +89,9 @@ __device__ __forceinline__ bf16x8 tr_fragment(const __bf16 *rows, int pitch, int
 // odd slabs of the chunk; their accumulators are added through LDS at the end.  Same waves per CU as two workgroups of four -- and
 // HALF the fp32 partials to write and to sum again (a partial costs 4 BN BC bytes per workgroup whatever the tile: at [81 600, 256] x
 // [81 600, 256] 128 chunks x 256 KB = 33 MB written and read back, against 84 MB of operands).
+// The body of a workgroup: `id` is the workgroup's index WITHIN ITS JOB (blockIdx.x for a launch that carries one job).
 template <int BN, int BC, int TS, int PF, int KG>
-__global__ __launch_bounds__(kThreadsW * KG)
-void twgrad_kernel(const TwgradArgs g)
+__device__ __forceinline__ void twgrad_body(const TwgradArgs &g, const int id)
 {
     constexpr int PN = BN + kRowPad, PC = BC + kRowPad;          // row pitches of the two slab images
     constexpr int TN = BN / 64, TC = BC / 64;                    // 32 x 32 blocks of a wave along n / c
@@ -102,7 +104,7 @@ void twgrad_kernel(const TwgradArgs g)
     const int tid = threadIdx.x & (kThreadsW - 1), lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
     const int wn = wave & 1, wc = wave >> 1;
     const int tiles = g.tiles_n * g.tiles_c;
-    const int id = blockIdx.x, grp = id >> 3;
+    const int grp = id >> 3;
     const int tile = grp % tiles, chunk = (grp / tiles) * 8 + (id & 7);
     if (chunk >= g.chunks) return;                               // (the chunk count was rounded up to a multiple of 8)
     const int n0 = (tile / g.tiles_c) * BN, c0 = (tile % g.tiles_c) * BC;
@@ -261,6 +263,46 @@ void twgrad_kernel(const TwgradArgs g)
     }
 }
 
+template <int BN, int BC, int TS, int PF, int KG>
+__global__ __launch_bounds__(kThreadsW * KG)
+void twgrad_kernel(const TwgradArgs g)
+{
+    twgrad_body<BN, BC, TS, PF, KG>(g, blockIdx.x);
+}
+
+// ---- grouped launches --------------------------------------------------------------------------------------------------------------
+// The weight gradients of a few thousand token rows (the decoder's 4 400, layer4's 3 840) are 128 workgroups of four or five slabs
+// each: ~11 us per launch of which one is memory time, the rest fill, drain and the boundary behind 8 MB of dirty partials.  Nothing
+// in the backward pass waits for them (chunk_sums.py), so their launches are collected and ONE launch carries up to kTwgradJobs jobs
+// of one instantiation.  The jobs' tables travel as the kernel's argument (chunk_sums_kernel's pattern, colsum.hip); a workgroup finds
+// its job by comparing blockIdx.x with the jobs' first workgroups -- scalar compares on a uniform value, read from the argument
+// segment -- and runs the body above with its index inside the job.  Each job keeps the plan() of a launch of its own: the same tiles,
+// chunks, slabs per chunk, partial layout -- the same bits.
+// XCD placement: every job's grid is a multiple of 8 workgroups (the chunk count rounded up to whole eights, times the tiles), so every
+// block0 is a multiple of 8 and (blockIdx.x & 7) == (id & 7): chunk c of a job still runs on XCD c % 8 with all its tiles, as the body
+// assumes (the launcher asserts it).
+constexpr int kTwgradJobs = 32;
+struct TwgradGroupJob {
+    TwgradArgs a;
+    int block0, pad_;                                            // the job's first workgroup in the launch
+};
+struct TwgradGroup {
+    TwgradGroupJob j[kTwgradJobs];
+    int njobs, pad_;
+};
+static_assert(sizeof(TwgradGroup) <= 3200, "the kernel argument stays well under 4 KB");
+
+template <int BN, int BC, int TS, int PF, int KG>
+__global__ __launch_bounds__(kThreadsW * KG)
+void twgrad_grouped_kernel(const TwgradGroup a)
+{
+    const int b = blockIdx.x;
+    int ji = 0;
+    for (int i = 1; i < a.njobs; ++i)
+        if (b >= a.j[i].block0) ji = i;                          // (block0 ascends: the last job that starts at or before b)
+    twgrad_body<BN, BC, TS, PF, KG>(a.j[ji].a, b - a.j[ji].block0);
+}
+
 struct TwgradPlan {
     int bn, bc, tiles_n, tiles_c, chunks, slabs, slabs_per_chunk, kg;
 };
@@ -295,12 +337,18 @@ TwgradPlan plan(int64_t T, int C, int N)
 }
 
 template <int BN, int BC, int KG>
+constexpr size_t twgrad_lds()
+{
+    constexpr size_t slabs_b = static_cast<size_t>(KG) * 2 * kSlab * ((BN + kRowPad) + (BC + kRowPad)) * 2;
+    constexpr size_t red_b = KG == 2 ? static_cast<size_t>(4) * ((BN / 64) * (BC / 64) * 16 * 64 + (BN / 64) * 32) * 4 : 0;
+    return slabs_b > red_b ? slabs_b : red_b;
+}
+
+template <int BN, int BC, int KG>
 hipError_t launch_tile(TwgradArgs g, hipStream_t st)
 {
     constexpr int TS = kSlab, PF = 2;
-    constexpr size_t slabs_b = static_cast<size_t>(KG) * 2 * TS * ((BN + kRowPad) + (BC + kRowPad)) * 2;
-    constexpr size_t red_b = KG == 2 ? static_cast<size_t>(4) * ((BN / 64) * (BC / 64) * 16 * 64 + (BN / 64) * 32) * 4 : 0;
-    constexpr size_t lds = slabs_b > red_b ? slabs_b : red_b;
+    constexpr size_t lds = twgrad_lds<BN, BC, KG>();
     auto kern = twgrad_kernel<BN, BC, TS, PF, KG>;
     static bool attr_set[64] = {};
     int dev_ = 0;
@@ -313,6 +361,26 @@ hipError_t launch_tile(TwgradArgs g, hipStream_t st)
     }
     const int64_t grid = static_cast<int64_t>((g.chunks + 7) / 8 * 8) * g.tiles_n * g.tiles_c;
     hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kThreadsW * KG), lds, st, g);
+    return hipGetLastError();
+}
+
+// one launch of the grouped kernel: the jobs of `a` (one instantiation, block0 filled in) on `grid` workgroups
+template <int BN, int BC, int KG>
+hipError_t launch_group(const TwgradGroup &a, int64_t grid, hipStream_t st)
+{
+    constexpr int TS = kSlab, PF = 2;
+    constexpr size_t lds = twgrad_lds<BN, BC, KG>();
+    auto kern = twgrad_grouped_kernel<BN, BC, TS, PF, KG>;
+    static bool attr_set[64] = {};
+    int dev_ = 0;
+    if (hipGetDevice(&dev_) != hipSuccess) dev_ = -1;
+    if (dev_ < 0 || dev_ >= 64 || !attr_set[dev_]) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 static_cast<int>(lds));
+        if (e != hipSuccess) return e;
+        if (dev_ >= 0 && dev_ < 64) attr_set[dev_] = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(grid)), dim3(kThreadsW * KG), lds, st, a);
     return hipGetLastError();
 }
 
@@ -540,6 +608,16 @@ hipError_t launch_tile32(Twgrad32Args g, hipStream_t st)
     return hipGetLastError();
 }
 
+TwgradArgs make_args(const TwgradPlan &p, const void *x, const void *dy, float *part, int64_t T, int C, int N, int64_t ldx, int64_t ldy, bool with_db)
+{
+    TwgradArgs g;
+    g.x = static_cast<const __bf16 *>(x); g.dy = static_cast<const __bf16 *>(dy); g.part = part;
+    g.T = T; g.ldx = ldx; g.ldy = ldy; g.part_stride = static_cast<int64_t>(N) * C + (with_db ? N : 0);
+    g.C = C; g.N = N; g.tiles_n = p.tiles_n; g.tiles_c = p.tiles_c; g.chunks = p.chunks; g.slabs = p.slabs; g.slabs_per_chunk = p.slabs_per_chunk;
+    g.with_db = with_db ? 1 : 0;
+    return g;
+}
+
 }  // namespace
 
 bool twgrad_supported(int64_t T, int C, int N, int64_t ldx, int64_t ldy, const void *x, const void *dy)
@@ -555,17 +633,66 @@ hipError_t twgrad_launch(const void *x, const void *dy, float *part, int64_t T, 
                          hipStream_t st)
 {
     const TwgradPlan p = plan(T, C, N);
-    TwgradArgs g;
-    g.x = static_cast<const __bf16 *>(x); g.dy = static_cast<const __bf16 *>(dy); g.part = part;
-    g.T = T; g.ldx = ldx; g.ldy = ldy; g.part_stride = static_cast<int64_t>(N) * C + (with_db ? N : 0);
-    g.C = C; g.N = N; g.tiles_n = p.tiles_n; g.tiles_c = p.tiles_c; g.chunks = p.chunks; g.slabs = p.slabs; g.slabs_per_chunk = p.slabs_per_chunk;
-    g.with_db = with_db ? 1 : 0;
+    const TwgradArgs g = make_args(p, x, dy, part, T, C, N, ldx, ldy, with_db);
     ProfileScope prof(11, conv_mflop(T, static_cast<int64_t>(C) * N), st, 2.0 * T * N * C / 1e6,
                       (2.0 * T * (N + C) + 4.0 * p.chunks * (static_cast<double>(N) * C + (with_db ? N : 0))) / 1e3);       // (+ the fp32 partials it writes)
     if (p.bn == 128 && p.bc == 128) return p.kg == 2 ? launch_tile<128, 128, 2>(g, st) : launch_tile<128, 128, 1>(g, st);
     if (p.bn == 128) return launch_tile<128, 64, 1>(g, st);
     if (p.bc == 128) return launch_tile<64, 128, 1>(g, st);
     return launch_tile<64, 64, 1>(g, st);
+}
+
+// Every job planned as a launch of its own (plan(): MDETR_TUNE's twgrad_kg / twgrad_wgs apply as there), sorted by instantiation, one
+// launch per instantiation and per kTwgradJobs jobs; within an instantiation the jobs keep the caller's order.
+hipError_t twgrad_grouped_launch(const TwgradJob *jobs, int njobs, hipStream_t st)
+{
+    if (njobs <= 0) return hipSuccess;
+    double mflop = 0.0, kbytes = 0.0;
+    int64_t key = 0;
+    std::vector<TwgradPlan> plans(static_cast<size_t>(njobs));
+    for (int i = 0; i < njobs; ++i) {
+        const TwgradJob &q = jobs[i];
+        const TwgradPlan &p = plans[static_cast<size_t>(i)] = plan(q.T, q.C, q.N);
+        key += conv_mflop(q.T, static_cast<int64_t>(q.C) * q.N);
+        mflop += 2.0 * q.T * q.N * q.C / 1e6;
+        kbytes += (2.0 * q.T * (q.N + q.C) + 4.0 * p.chunks * (static_cast<double>(q.N) * q.C + (q.with_db ? q.N : 0))) / 1e3;
+    }
+    ProfileScope prof(11, key, st, mflop, kbytes);                // the jobs' work summed: bench.py's family table keeps adding up
+    static const int inst[5][3] = {{128, 128, 1}, {128, 128, 2}, {128, 64, 1}, {64, 128, 1}, {64, 64, 1}};
+    for (int k = 0; k < 5; ++k) {
+        TwgradGroup a;
+        a.njobs = 0; a.pad_ = 0;
+        int64_t grid = 0;
+        const auto send = [&]() -> hipError_t {
+            if (a.njobs == 0) return hipSuccess;
+            const hipError_t e = k == 0 ? launch_group<128, 128, 1>(a, grid, st) : k == 1 ? launch_group<128, 128, 2>(a, grid, st)
+                               : k == 2 ? launch_group<128, 64, 1>(a, grid, st) : k == 3 ? launch_group<64, 128, 1>(a, grid, st)
+                               : launch_group<64, 64, 1>(a, grid, st);
+            a.njobs = 0;
+            grid = 0;
+            return e;
+        };
+        for (int i = 0; i < njobs; ++i) {
+            const TwgradPlan &p = plans[static_cast<size_t>(i)];
+            if (p.bn != inst[k][0] || p.bc != inst[k][1] || p.kg != inst[k][2]) continue;
+            const TwgradJob &q = jobs[i];
+            const int64_t blocks = static_cast<int64_t>((p.chunks + 7) / 8 * 8) * p.tiles_n * p.tiles_c;
+            if (a.njobs == kTwgradJobs || grid + blocks > 0x7fffffff) {
+                const hipError_t e = send();
+                if (e != hipSuccess) return e;
+            }
+            // (whole eights: chunk c of every job on XCD c % 8, see the kernel)
+            if (grid % 8 != 0 || blocks % 8 != 0) return hipErrorInvalidValue;
+            TwgradGroupJob &gj = a.j[a.njobs++];
+            gj.a = make_args(p, q.x, q.dy, q.part, q.T, q.C, q.N, q.C, q.N, q.with_db != 0);
+            gj.block0 = static_cast<int>(grid);
+            gj.pad_ = 0;
+            grid += blocks;
+        }
+        const hipError_t e = send();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 bool twgrad_f32_supported(int64_t T, int C, int N, int64_t ldx, int64_t ldy, const void *x, const void *dy)

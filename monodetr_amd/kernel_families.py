@@ -14,7 +14,7 @@ AUTOTUNE_SWITCHES = ("MDETR_FUSED_LOSSES", "MDETR_FUSED_ADAMW", "MDETR_MSDA_PROL
                      "MDETR_FUSED_EPILOGUE", "MDETR_GEMM_RELU", "MDETR_CONV3X3", "MDETR_GROUP_NORM", "MDETR_SMALL_WGRAD",
                      "MDETR_CONV_STRIDED", "MDETR_CONV_WGRAD", "MDETR_CONV_STEM", "MDETR_TGEMM", "MDETR_WFOLD", "MDETR_RELU_PREMASK",
                      "MDETR_HEADS", "MDETR_CHUNK_SUMS", "MDETR_HEAD_TAIL", "MDETR_TGEMM_F32", "MDETR_TWGRAD_F32",
-                     "MDETR_CONV3X3_F32", "MDETR_CONV_WGRAD_F32", "MDETR_CONV_STRIDED_F32", "MDETR_CONV_STEM_F32", "MDETR_PARAM_PACK",
+                     "MDETR_CONV3X3_F32", "MDETR_CONV_WGRAD_F32", "MDETR_CONV_STRIDED_F32", "MDETR_CONV_STEM_F32", "MDETR_PARAM_PACK", "MDETR_TWGRAD_GROUPED",
                      "MDETR_CONV_WGRAD_S2_F32")
 ALL_SWITCHES = AUTOTUNE_SWITCHES
 # The measured configuration.  family -> the GPU tests that hold it to the default path / the framework operators
@@ -46,6 +46,7 @@ SWITCH_TESTS = {
     "MDETR_HEAD_TAIL": "test_sgemm_gpu.py::test_head_tail_*, test_sgemm_gpu.py::test_training_step_with_the_head_tail_*, test_head_tail_cases_gpu.py::test_head_tail_*",
     "MDETR_CHUNK_SUMS": "test_colsum_gpu.py::test_chunk_sums_*, test_colsum_gpu.py::test_deferred_chunk_sums_*, test_chunk_sums_tall_gpu.py::test_chunk_sums_*",
     "MDETR_PARAM_PACK": "test_wpack_gpu.py::test_*",
+    "MDETR_TWGRAD_GROUPED": "test_twgrad_grouped_gpu.py::test_*",
     "MDETR_CONV3X3": "test_conv3x3_kernel_matches_the_library_convolution, test_training_step_with_the_conv3x3_kernel_*, test_conv3x3_module_with_a_trainable_bias_*, test_exact_products_gpu.py::test_exact_conv3x3_*",
 }
 COMMITTED_SWITCHES = {
@@ -83,10 +84,13 @@ COMMITTED_SWITCHES = {
     # list; DESIGN.md 3.5 records what was measured.
     # MDETR_PARAM_PACK: the transformer's packed / summed projection parameters of a forward pass from one launch and the encoder's
     # level positions as one [S, C] tensor from one more (csrc/wpack.hip), bit-identical; DESIGN.md 3.7 records the launches and the step.
+    # MDETR_TWGRAD_GROUPED: inside chunk_sums.deferred() the bf16 token weight gradients of at most 8 192 rows are registered and sent
+    # together at the flush points (mdetr_token_wgrad_grouped), ahead of their chunk sums; bit-identical partials.  bf16 only:
+    # the fp32 lists have no bf16 token weight gradient.  DESIGN.md 3.4 records the launches and the step.
     "bf16": ("MDETR_FUSED_LOSSES", "MDETR_FUSED_ADAMW", "MDETR_FUSED_LN", "MDETR_MSDA_PROLOGUE", "MDETR_MSDA_BF16",
              "MDETR_FUSED_EPILOGUE", "MDETR_GEMM_RELU", "MDETR_CONV3X3", "MDETR_GROUP_NORM", "MDETR_SMALL_WGRAD",
              "MDETR_CONV_WGRAD", "MDETR_CONV_STRIDED", "MDETR_CONV_STEM", "MDETR_TGEMM", "MDETR_WFOLD", "MDETR_RELU_PREMASK", "MDETR_HEADS",
-             "MDETR_CHUNK_SUMS", "MDETR_HEAD_TAIL", "MDETR_PARAM_PACK"),
+             "MDETR_CHUNK_SUMS", "MDETR_HEAD_TAIL", "MDETR_PARAM_PACK", "MDETR_TWGRAD_GROUPED"),
     "fp32": ("MDETR_FUSED_LOSSES", "MDETR_FUSED_ADAMW", "MDETR_FUSED_LN", "MDETR_MSDA_PROLOGUE",
              "MDETR_FUSED_EPILOGUE", "MDETR_GEMM_RELU", "MDETR_GROUP_NORM", "MDETR_SMALL_WGRAD", "MDETR_HEADS",
              "MDETR_HEAD_TAIL", "MDETR_PARAM_PACK"),
@@ -132,6 +136,7 @@ def apply_switches(names):
     conv_taps_ext.ENABLED_F32 = "MDETR_CONV_STRIDED_F32" in names
     conv_wgrad_ext.ENABLED = "MDETR_CONV_WGRAD" in names
     conv_wgrad_ext.ENABLED_F32 = "MDETR_TWGRAD_F32" in names
+    conv_wgrad_ext.GROUPED = "MDETR_TWGRAD_GROUPED" in names
     conv_wgrad_ext.ENABLED_CONV_F32 = "MDETR_CONV_WGRAD_F32" in names
     conv_wgrad_ext.ENABLED_CONV_S2_F32 = "MDETR_CONV_WGRAD_S2_F32" in names
     conv_stem_ext.ENABLED = "MDETR_CONV_STEM" in names
